@@ -13,10 +13,16 @@ the workload's ONE genome (weak scaling: n reads per GPU; coverage grows with
 N) and k-mers are routed to the GPU that owns their canonical mmer with an
 RCCL all-to-all (genome-assembly_amd/kbin/dist.py).
 
-Prints ONE JSON line on rank 0 (contract in the task statement); extra
-objects: "roofline" for the dominant kernel (bin_kernel; scan_insert_kernel
-on the table engine) and "cpu_baseline" (the compiled reference, with the C
-port beside it, on a bounded sample of the same workload, rank 0 only).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run
+sets up, warms up, times --steps steps and prints the line: the headline
+value, "ms_per_step", and what the timed steps' own events give ("roofline"
+for the dominant kernel -- bin_kernel; scan_insert_kernel on the table engine
+-- "phases_ms", "paths", "result").  --dump-outputs DIR writes the last timed
+step's result as .npy files (dump_outputs).  --full adds every leg that takes
+runs of its own: the replay steps, the untimed all-events phase step, the
+host-ingest leg, the C3 capacity leg (N > 1: the C4 and C5 legs) and
+"cpu_baseline" (the compiled reference, with the C port beside it, on a
+bounded sample of the same workload, rank 0 only).
 """
 from __future__ import annotations
 
@@ -602,6 +608,61 @@ def multi_capacity_leg(name, rank, world, local, dist, backend, steps=2, warmup=
     return out
 
 
+DUMP_SEED = 20250101     # the sample of --dump-outputs: the same entries every run
+DUMP_ENTRIES = 1 << 18   # entries sampled (16.8 MB of float64 over the per-entry files)
+DUMP_IDS = 1 << 22       # ids of the sampled entries' lists kept (33.6 MB of float64)
+
+
+def _words32(x):
+    """uint64 array -> float64 [..., 2] of its high and low 32-bit words (exact)"""
+    x = np.asarray(x, dtype=np.uint64)
+    return np.stack([x >> np.uint64(32), x & np.uint64(0xFFFFFFFF)], axis=-1).astype(np.float64)
+
+
+def dump_outputs(eng, out_dir):
+    """--dump-outputs: the result the engine holds after the last timed step
+    (kb_export: what a caller of the timed path receives; P > 1: the step's
+    last pass; N > 1: rank 0's share), as float64 .npy files under out_dir,
+    about 50 MB in all.  The device CSR's entry order is not fixed from run
+    to run, so entries are taken in canonical dump order (Result.canonical:
+    bytewise (mmer, kmer) ascending) and a fixed seeded sample of them is
+    written, the same positions for the same entry count:
+      totals.npy       [n_entries, n_ids, n_kmers, n_distinct] of the whole result
+      digest.npy       kb_digest of the whole result, [4, 2]: 32-bit words (high, low)
+      entry_index.npy  the sampled entries' canonical positions, ascending
+      mmer.npy, count.npy, offset.npy  of the sampled entries (offset: the
+                       entry's first id in the canonical id array)
+      kmer.npy         [S, 4]: kmer_hi and kmer_lo as 32-bit words (high, low)
+      ids.npy          the id lists of the first sampled entries, concatenated
+                       (whole lists, DUMP_IDS ids at most; count.npy splits them)
+    """
+    res = eng.export()
+    dig = eng.digest()
+    out = pathlib.Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    order = np.lexsort((res.kmer_lo, res.kmer_hi, res.mmer))[::-1]
+    n = len(order)
+    rng = np.random.default_rng(DUMP_SEED)
+    pick = np.sort(rng.choice(n, size=min(n, DUMP_ENTRIES), replace=False)) if n else np.zeros(0, np.int64)
+    canon_off = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(res.count[order], dtype=np.int64, out=canon_off[1:])
+    e = order[pick]
+    cnt = res.count[e].astype(np.int64)
+    j = int(np.searchsorted(np.cumsum(cnt), DUMP_IDS, side="right"))  # whole lists within DUMP_IDS
+    starts, c = res.offset[:-1][e[:j]].astype(np.int64), cnt[:j]
+    idx = np.repeat(starts - (np.cumsum(c) - c), c) + np.arange(int(c.sum()), dtype=np.int64)
+    files = {"totals": np.array([n, len(res.ids), res.n_kmers, res.n_distinct], dtype=np.float64),
+             "digest": _words32(np.array(dig, dtype=np.uint64)),
+             "entry_index": pick.astype(np.float64),
+             "mmer": res.mmer[e].astype(np.float64),
+             "kmer": np.concatenate([_words32(res.kmer_hi[e]), _words32(res.kmer_lo[e])], axis=-1),
+             "count": cnt.astype(np.float64),
+             "offset": canon_off[:-1][pick].astype(np.float64),
+             "ids": res.ids[idx].astype(np.float64)}
+    for name, a in files.items():
+        np.save(out / f"{name}.npy", a)
+
+
 def main():
     # stdout carries exactly ONE JSON line (rank 0): native libraries print to
     # fd 1 (RCCL's version banner, gloo's connection notes), so fd 1 points at
@@ -613,6 +674,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every leg that takes runs of its own: the replay "
+                         "steps, the all-events phase step, the host-ingest leg, the C3 capacity leg (N > 1: "
+                         "the C4 and C5 legs) and the CPU baseline; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's result (a fixed seeded sample of its "
+                         "entries and id lists, its totals and digest) as DIR/<name>.npy; see dump_outputs")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c2",
                     help="SURVEY §8(d) configuration (c2: the headline 1M x 150 bp; c3: "
                          "100M x 150 bp on one GPU in mmer-partitioned passes; c4/c5: the "
@@ -630,21 +698,21 @@ def main():
     ap.add_argument("--digest", action="store_true",
                     help="after timing, one more step reporting kb_digest summed over the passes")
     ap.add_argument("--cpu-sample", type=int, default=300_000,
-                    help="reads timed on the CPU oracle (0 = skip)")
+                    help="--full: reads timed on the CPU oracle (0 = skip)")
     ap.add_argument("--ref-sample", type=int, default=120_000,
-                    help="reads timed on the compiled reference (oracle/_ref; 0 = port only)")
+                    help="--full: reads timed on the compiled reference (oracle/_ref; 0 = port only)")
     ap.add_argument("--input", choices=("auto", "fresh", "replay"), default="auto",
                     help="fresh: every step bins new reads of the same genome (all sets generated before "
                          "timing); replay: the same reads every step; auto: fresh when the sets fit in "
                          "5%% of the HBM")
     ap.add_argument("--host-input", dest="host_input", action="store_true", default=True,
-                    help=argparse.SUPPRESS)  # (the host leg is on by default; kept for older command lines)
+                    help=argparse.SUPPRESS)  # (the host leg is part of --full; kept for older command lines)
     ap.add_argument("--no-host-input", dest="host_input", action="store_false",
-                    help="N=1: skip the host-ingest leg (kb_submit of host ASCII, finalize, kb_export, "
-                         "H2D and D2H reported separately; on by default)")
+                    help="--full at N=1: skip the host-ingest leg (kb_submit of host ASCII, finalize, "
+                         "kb_export, H2D and D2H reported separately)")
     ap.add_argument("--no-capacity", dest="capacity", action="store_false",
-                    help="N=1: skip the C3 capacity leg (100M x 150 bp in 4 passes, digest-checked; on by "
-                         "default)")
+                    help="--full at N=1: skip the C3 capacity leg (100M x 150 bp in 4 passes, "
+                         "digest-checked); N > 1: skip the C4 and C5 legs")
     ap.add_argument("--multi-legs", action="store_true",
                     help="N=1 with --routed: run the N > 1 run's C4 and C5 legs through the one-rank group "
                          "(a full-size rehearsal of their memory and time)")
@@ -807,7 +875,9 @@ def main():
     # the Python side of the timed steps kept raw structs: convert them now, and
     # read a one-pass step's export (the same shape every step) from the last
     ex_last = eng.export_device()
-    if light:  # the phases: one untimed step with every phase event
+    if args.dump_outputs and rank == 0:  # (before any later leg steps the engine again)
+        dump_outputs(eng, args.dump_outputs)
+    if light and args.full:  # the phases: one untimed step with every phase event
         eng.set_timing(True)
         step()
         drain()
@@ -829,9 +899,10 @@ def main():
     # or -- timed with bin_kernel's events only -- the last warmup step's
     phases = {k: round(float(np.mean([sum(t[k] for _, t in st) for st in ([phase_log] if light else steps_log)])), 4)
               for k in ("scan_insert_ms", "sort_ms", "runs_ms", "emit_ms", "total_ms")}
-    phases["source"] = "one untimed step after the timed ones (all phase events)" if light else "timed steps"
+    phases["source"] = (("one untimed step after the timed ones (all phase events)" if args.full else
+                         "the last warmup step (all phase events)") if light else "timed steps")
     replay = None
-    if fresh and args.steps:
+    if args.full and fresh and args.steps:
         # the same number of steps replaying one set (round 1's headline mode)
         drain()
         barrier()
@@ -887,7 +958,8 @@ def main():
                    "engine": {1: "table", 2: "binned"}.get(int(tim[-1]["engine"]), "?"),
                    "bins": int(tim[-1]["n_bins"]), "superkmers": int(tim[-1]["n_superkmers"])},
     }
-    legs = (world > 1 or (args.routed and args.multi_legs)) and args.capacity and args.workload == "c2"
+    legs = (((world > 1 and args.full) or (args.routed and args.multi_legs)) and args.capacity
+            and args.workload == "c2")
     if legs:
         # BASELINE's multi-GPU configurations as specified (the headline stays
         # C2 weak scaling: the same per-GPU work at every N); the main leg's
@@ -900,13 +972,13 @@ def main():
             out["capacity"][name] = multi_capacity_leg(name, rank, world, local, dist, backend, scale=scale)
             if rank == 0:
                 print(json.dumps({name: out["capacity"][name]}), file=sys.stderr, flush=True)
-    if world == 1 and args.host_input and P == 1 and not legs:
+    if args.full and world == 1 and args.host_input and P == 1 and not legs:
         out["host_input"] = host_input_leg(sets[0][0], sets[0][1], n, wpr, L, K, M, args.cutoff, local)
-    if world == 1 and args.capacity and args.workload == "c2" and not args.routed:
+    if args.full and world == 1 and args.capacity and args.workload == "c2" and not args.routed:
         out["capacity"] = capacity_leg(local)
     if rank == 0 and world == 1 and args.dropin and P == 1 and not legs:
         out["dropin"] = dropin_leg(sets[0][0], sets[0][1], n, wpr, L, K, M, args.cutoff, local)
-    if rank == 0 and world == 1 and args.cpu_sample > 0 and not legs:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0 and not legs:
         out["cpu_baseline"] = cpu_baseline(sets[0][0], sets[0][1], n, min(args.cpu_sample, n), wpr, L, K, M,
                                            args.cutoff, args.ref_sample)
     if rank == 0:

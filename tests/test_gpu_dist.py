@@ -535,7 +535,7 @@ def test_bench_multi_gpu_capacity_rehearsal(tmp_path, engine, transport):
     env.pop("KB_ENGINE", None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), str(kbin.REPO_ROOT / "bench.py"),
-                        "--gpus", "2", "--steps", "2", "--warmup", "1", "--reads", "100000"],
+                        "--gpus", "2", "--steps", "2", "--warmup", "1", "--reads", "100000", "--full"],
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

@@ -28,6 +28,7 @@
 
 #include "../../include/kbin.h"
 #include "kbin_internal.h"
+#include "kbin_hash.h"
 
 using namespace kb;
 
@@ -373,8 +374,9 @@ extern "C" int kb_create(const kb_params* params, kb_ctx** out) {
     if (p.M < 1 || p.M > 8)
         return fail(KB_EINVAL, "M=%d outside [1,8] (power_val, binning.c:17)", p.M);
     // (K < 2M: the reference's incremental branch, binning.c:992-1021, is
-    // live -- the binned engine's record pass walks it, reads of <= 512 bp,
-    // one GPU; kb_finalize and the routing calls check the rest)
+    // live -- the binned engine's record pass walks it, any read length; its
+    // records are routable, the complement flag in bit 60 of their header
+    // (ROUTED_REV_BIT); kb_finalize and the routing calls check the rest)
     if (p.K > 63) return fail(KB_EINVAL, "K=%d > 63 unsupported", p.K);
     // (a k-mer holds its signature mmer: K >= M, binning.c:931-936 reads M bases
     // of every k-mer; the incremental walk starts at K - M >= 0)
@@ -757,7 +759,7 @@ static double now_ms() {
         if (_on) fprintf(stderr, "[kb] " __VA_ARGS__);          \
     } while (0)
 
-// the binned engine (kbin_bins.hip) serves K <= 63 unless the table engine is
+// the binned engine (kbin_sk.hip, kbin_plan.hip, kbin_bins.hip, kbin_lists.hip) serves K <= 63 unless the table engine is
 // forced (flag, or KB_ENGINE=table).  Two-word k-mers (K > 31) take only its
 // bucketed record path: reads of <= 512 bp (or received super-k-mers), no
 // forced radix path, and no bucket overflow so far -- elsewhere the table
@@ -820,8 +822,8 @@ static void owner_table_host(int K, int M, uint32_t n_dest, uint32_t part, uint3
     std::vector<double> load(n_dest, 0.0);
     for (uint32_t i = half; i-- > 0;) {  // the weight grows with i: heaviest first
         const uint32_t mm = half + i;
-        if (part_n > 1 && sk_hash_dest(mm, part_n, 0x9E3779B97F4A7C15ull) != part) {
-            out[i] = (uint8_t)sk_hash_dest(mm, n_dest, 0x5851F42D4C957F2Dull);
+        if (part_n > 1 && dest_of(mm, part_n, PART_SALT) != part) {
+            out[i] = (uint8_t)dest_of(mm, n_dest, OWNER_SALT);
             continue;
         }
         uint32_t r = 0;
@@ -1000,12 +1002,12 @@ static int scatter_regions(kb_ctx* c, uint32_t n_dest, uint64_t* d_regions, uint
 
 extern "C" int kb_route_scatter(kb_ctx* c, uint32_t n_dest, uint64_t* d_regions, uint64_t region_cap,
                                 uint64_t* h_counts) {
-    return scatter_regions(c, n_dest, d_regions, region_cap, h_counts, 0x5851F42D4C957F2Dull, false);
+    return scatter_regions(c, n_dest, d_regions, region_cap, h_counts, OWNER_SALT, false);
 }
 
 extern "C" int kb_split_passes(kb_ctx* c, uint32_t n_parts, uint64_t* d_regions, uint64_t region_cap,
                                uint64_t* h_counts) {
-    return scatter_regions(c, n_parts, d_regions, region_cap, h_counts, 0x9E3779B97F4A7C15ull, true);
+    return scatter_regions(c, n_parts, d_regions, region_cap, h_counts, PART_SALT, true);
 }
 
 static int scatter_regions(kb_ctx* c, uint32_t n_dest, uint64_t* d_regions, uint64_t region_cap,
@@ -1049,7 +1051,7 @@ static int scatter_regions(kb_ctx* c, uint32_t n_dest, uint64_t* d_regions, uint
         a.read_ids = affine ? nullptr : c->read_ids.p;
         a.id_off = (uint32_t)(affine ? id_c : 0);
         a.G = n_dest;
-        a.dest_salt = salt;  // owner_of (kbin_kernels.hip), or in_part's PART_SALT (kbin_bins.hip)
+        a.dest_salt = salt;  // OWNER_SALT or PART_SALT (kbin_hash.h)
         if (!by_pass) {  // ranks: the pass's owner table (passes: the partition hash)
             const int orc = owner_map_dev(c, n_dest, &a.owner_map);
             if (orc) return orc;
@@ -1172,8 +1174,8 @@ static int log2u(uint64_t x) {
 }
 
 // ---------------------------------------------------------------------------
-// binned engine (kbin_bins.hip): super-k-mers -> sort by mmer -> one LDS
-// table per bin.  Eligible for K <= 31 reads binned here, no first-occurrence
+// binned engine: super-k-mers (kbin_sk.hip) -> sort by mmer (kbin_plan.hip's
+// bucket ordering, or onesweep) -> one LDS table per bin (kbin_bins.hip).  Eligible for K <= 31 reads binned here, no first-occurrence
 // tracking.
 // ---------------------------------------------------------------------------
 
@@ -1368,8 +1370,8 @@ static int bmap_build(kb_ctx* c, uint32_t NB, double rho, bool prior = false) {
     // that order within the bin budget
     std::vector<std::pair<double, uint32_t>> seen;
     for (uint32_t i = 0; i < half; i++) {
-        h[i] = (uint32_t)sk_hash_dest(half + i, NB, sk_bucket_salt());  // unseen (or another pass's): hash
-        if (c->part_n > 1 && sk_hash_dest(half + i, c->part_n, 0x9E3779B97F4A7C15ull) != c->part) continue;
+        h[i] = (uint32_t)dest_of(half + i, NB, BUCKET_SALT);  // unseen (or another pass's): hash
+        if (c->part_n > 1 && dest_of(half + i, c->part_n, PART_SALT) != c->part) continue;
         const double w = i < c->mmer_w.size() ? (double)c->mmer_w[i] : 0.0;
         // (a negligible mmer keeps its hash bucket: no packing item)
         if (w > 0 && w >= mean / 512.0) seen.push_back({w, i});
@@ -1578,7 +1580,7 @@ static int bmap_prior(kb_ctx* c, uint32_t NB) {
     double tot = 0, mine = 0;
     for (uint32_t i = 0; i < half; i++) {
         tot += p[i];
-        if (c->part_n <= 1 || sk_hash_dest(half + i, c->part_n, 0x9E3779B97F4A7C15ull) == c->part) mine += p[i];
+        if (c->part_n <= 1 || dest_of(half + i, c->part_n, PART_SALT) == c->part) mine += p[i];
     }
     // reads scanned for one partition emit only its records; received ones are its own
     const double R_part = reads_part ? R_est * mine / std::max(tot, 1e-300) : R_est;
@@ -1738,7 +1740,7 @@ static int binned_buckets(kb_ctx* c, uint32_t NB, bool received, bool zeroed, ui
                 a.region_base = use_base ? c->rbase.p : nullptr;
                 a.dest_ctr = c->bfill.p;
                 a.G = NB;
-                a.dest_salt = sk_bucket_salt();
+                a.dest_salt = BUCKET_SALT;
                 a.rw = (int)RWD;  // header + span words
                 a.bucket_map = bmap;
                 a.sub_map = bsub;
@@ -1898,7 +1900,7 @@ static void offset_cuts(int K, int M, uint8_t (&cut)[5][17]) {
     uint64_t x = 0x243F6A8885A308D3ull;
     for (int read = 0; read < 400; read++) {  // (~50 K occurrences: once per context, in its first finalize)
         for (int i = 0; i < L; i++) {
-            x += 0x9E3779B97F4A7C15ull;
+            x += GOLDEN64;
             uint64_t z = x;
             z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
             z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;

@@ -1,15 +1,17 @@
-// kbin_bins.hip -- the binned engine ("v2") for K <= 31.
+// kbin_bins.hip -- the binned engine ("v2"): its bin kernels.
 //
 // The reference's level-1 key is the signature mmer (binning.c:1045): every
 // (mmer, kmer) entry lives in exactly one mmer bin, and prune_kmers runs per
 // mmer table (binning.c:1085, 1136).  v2 uses that as the unit of locality:
 //
-//   sk_count / sk_write  one wavefront per read walks the sticky signature
-//                        chain (as scan_insert does) and emits one record per
-//                        super-k-mer (run of k-mers sharing a signature):
-//                        payload {ord | i0 | n | sig_off}, sort key (mmer, t)
-//   onesweep             stable sort of the keys by mmer (2 passes at M=7)
-//   heads                bin boundaries
+//   sk_count / sk_write  (kbin_sk.hip) one wavefront per read walks the sticky
+//                        signature chain (as scan_insert does) and emits one
+//                        record per super-k-mer (run of k-mers sharing a
+//                        signature): payload {ord | i0 | n | sig_off}, sort
+//                        key (mmer, t)
+//   onesweep + heads     stable sort of the keys by mmer and the bin boundaries
+//                        (kbin_kernels.hip), or bucket_kernel (kbin_plan.hip,
+//                        with the bins' processing order)
 //   bin_kernel           ONE WORKGROUP PER BIN: an LDS open-addressed table
 //                        keyed by the k-mer alone (the mmer is the bin -- this
 //                        is the per-mmer bucket of the north star), counts by
@@ -17,6 +19,7 @@
 //                        and per-key reverse-call-order lists, all LDS/L2-local.
 //                        A bin whose keys overflow the LDS table is split by
 //                        k-mer hash into sub-partitions, recursively.
+//   lists_kernel         (kbin_lists.hip) the lists the bin kernel left unsorted
 //
 // Nothing in the hot loops touches HBM at random except the read-word gathers
 // (L2/MALL-resident packed reads) and the output writes.
@@ -26,871 +29,11 @@
 
 #include <hip/hip_ext.h>
 
-#define KB_BINS_TU  // (kbin_internal.h: BinArgs pointers are global in this file's device code)
+#define KB_BINARGS_GLOBAL  // (kbin_internal.h: this file's kernels dereference BinArgs)
 #include "kbin_internal.h"
-#include "kbin_device.h"
+#include "kbin_sort.h"
 
 namespace kb {
-
-// ---------------------------------------------------------------------------
-// phase A: super-k-mer extraction
-// ---------------------------------------------------------------------------
-// One segment of the sticky chain per call: leftmost strict argmax of the
-// complement-canonical mmer score over [lo, lo + K - M]  (binning.c:922-988).
-DEV void segment_at(const uint64_t* sw, int lo, int lane, int W, int M, uint32_t maskM,
-                    uint32_t halfM, int& sig, uint32_t& canon) {
-    const int d = (lane - lo) & 63;
-    uint32_t key = 0;
-    if (d < W) {
-        const int p = lo + d;
-        const uint32_t s = (uint32_t)(window64(sw, p) >> (64 - 2 * M));
-        const uint32_t c = s >= halfM ? s : maskM - s;
-        key = (c << 16) | (0xFFFFu - (uint32_t)p);
-    }
-    key = wave_max_u32(key);
-    sig = rfl((int)(0xFFFFu - (key & 0xFFFFu)));
-    canon = (uint32_t)rfl((int)(key >> 16));
-}
-
-// QK (K < 2M): the reference's per-k-mer signature state, binning.c:922-1021.
-// The incremental branch (992-1021: j runs K-M .. M-1) is live: it appends
-// bases to a score it never trims, in int arithmetic that wraps, so the
-// signature can move to the k-mer's last M bases and is_rev follow the
-// polluted scores.  One lane walks its read k-mer by k-mer with that state;
-// a record is a run of k-mers with one signature position (`next`).
-struct QWalk {
-    int32_t s = 0, r = 0, m = 0;  // score, rev_score, max_score
-    bool rev = false;
-    int sig = -1, i = -1;         // signature position, last k-mer stepped
-    DEV uint32_t code(const uint64_t* sw, int p, int M, uint32_t maskM) const {
-        return (uint32_t)(window64(sw, p) >> (64 - 2 * M)) & maskM;
-    }
-    DEV void step(const uint64_t* sw, int k, int K, int M, uint32_t maskM) {
-        if (k > sig) {  // a fresh window (binning.c:922-989): leftmost strict argmax
-            uint32_t sm = code(sw, k, M, maskM);
-            int32_t sc = (int32_t)sm, rv = (int32_t)(maskM - sm);
-            m = sc > rv ? sc : rv;
-            rev = !(sc > rv);
-            sig = k;
-            for (int p = k + 1; p <= k + K - M; p++) {
-                sm = code(sw, p, M, maskM);
-                sc = (int32_t)sm;
-                rv = (int32_t)(maskM - sm);
-                if ((sc > rv ? sc : rv) > m) {
-                    m = sc > rv ? sc : rv;
-                    rev = !(sc > rv);
-                    sig = p;
-                }
-            }
-            s = sc;
-            r = rv;
-        } else {  // the incremental branch (binning.c:992-1021)
-            for (int j = K - M; j < M; j++) {
-                const uint32_t v = (uint32_t)(window64(sw, k + j) >> 62);
-                s = (int32_t)((uint32_t)s * 4u + v);
-                r = (int32_t)((uint32_t)r * 4u + 3u - v);
-            }
-            if ((s > r ? s : r) > m) {
-                m = s > r ? s : r;
-                rev = !(s > r);
-                sig = k + K - M;
-            }
-        }
-        i = k;
-    }
-    // the record starting at k-mer lo: its signature and complement flag, and
-    // the first k-mer of the next record
-    DEV void next(const uint64_t* sw, int lo, int nK, int K, int M, uint32_t maskM, int& rsig, bool& rrev,
-                  int& e) {
-        if (i < lo) step(sw, lo, K, M, maskM);
-        rsig = sig;
-        rrev = rev;
-        e = lo + 1;
-        while (e < nK) {
-            step(sw, e, K, M, maskM);
-            if (sig != rsig) break;
-            e++;
-        }
-    }
-};
-
-constexpr uint64_t OWNER_SALT = 0x5851F42D4C957F2Dull;   // rank of a mmer (= owner_of(), kbin_kernels.hip)
-constexpr uint64_t BUCKET_SALT = 0x2545F4914F6CDD1Dull;  // bucket of a mmer inside one rank (independent)
-constexpr uint64_t PART_SALT = 0x9E3779B97F4A7C15ull;    // pass of a mmer (kb_set_partition; independent)
-uint64_t sk_bucket_salt() { return BUCKET_SALT; }
-
-DEV uint32_t dest_of(uint32_t mmer, uint32_t G, uint64_t salt) {
-    return (uint32_t)((mix64((uint64_t)mmer + salt) >> 32) % G);
-}
-uint32_t sk_hash_dest(uint32_t mmer, uint32_t G, uint64_t salt) {
-    uint64_t x = (uint64_t)mmer + salt;  // mix64 (kbin_device.h), host side
-    x ^= x >> 30;
-    x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27;
-    x *= 0x94d049bb133111ebull;
-    x ^= x >> 31;
-    return (uint32_t)((x >> 32) % G);
-}
-
-// CPU-callable check of the guard above (tests/test_abi.py): the first
-// destination of a depth-0 record of code `canon` on a bucketed pass with map
-// `map` over NB buckets -- the map's bucket for a canonical code, the hash
-// route for any other (never map[canon - half] with canon < half)
-extern "C" uint32_t kb_internal_map_dest(const uint32_t* map, uint32_t canon, int M, uint32_t NB) {
-    if (!map || !bm_has_entry(canon, M)) return sk_hash_dest(canon, NB, BUCKET_SALT);
-    return map[canon - (1u << (2 * M - 1))] & 1023u;
-}
-DEV uint32_t owner_of_mmer(uint32_t mmer, uint32_t G) { return dest_of(mmer, G, OWNER_SALT); }
-// a pass keeps the super-k-mers of its own mmer partition
-DEV bool in_part(uint32_t mmer, uint32_t part, uint32_t part_n) {
-    return part_n <= 1 || dest_of(mmer, part_n, PART_SALT) == part;
-}
-
-template <bool WRITE, bool QK = false>
-__global__ __launch_bounds__(256) void sk_kernel(SkScanArgs A) {
-    extern __shared__ __attribute__((aligned(16))) uint64_t smem[];
-    const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
-    const int RW = A.RW, K = A.K, M = A.M;
-    const int W = K - M + 1;
-    const uint32_t maskM = (1u << (2 * M)) - 1u;
-    const uint32_t halfM = 1u << (2 * M - 1);
-    uint64_t* sw = smem + wid * (RW + 2);  // two zero words: span windows never leave the read
-    const uint64_t nwaves = (uint64_t)gridDim.x * 4;
-    uint64_t kmers = 0;
-    for (uint64_t r = (uint64_t)blockIdx.x * 4 + wid; r < A.n_reads; r += nwaves) {
-        const int L = rfl((int)A.lens[r]);
-        const int nK = L - K + 1;
-        uint32_t nseg = 0;
-        if (nK > 0) {
-            wave_sync();
-            for (int w = lane; w < RW + 2; w += 64) sw[w] = w < RW ? A.words[r * RW + w] : 0ull;
-            wave_sync();
-            const uint64_t rbase = WRITE ? A.rec_base[r] : 0;
-            const uint64_t ordv = (uint64_t)(A.ord_base + (uint32_t)r);
-            int lo = 0;
-            QWalk qw;  // (QK: lane 0's walk, its records broadcast to the wave)
-            while (lo < nK) {
-                int sig, nlo;
-                uint32_t canon;
-                bool qrev = false;
-                if (QK) {
-                    int rs = 0, e = 0;
-                    bool rv = false;
-                    if (lane == 0) qw.next(sw, lo, nK, K, M, maskM, rs, rv, e);
-                    sig = __shfl(rs, 0, 64);
-                    nlo = __shfl(e, 0, 64);
-                    qrev = __shfl((int)rv, 0, 64) != 0;
-                    const uint32_t sm = qw.code(sw, sig, M, maskM);
-                    canon = qrev ? maskM - sm : sm;  // the bin's mmer code (not canonical)
-                } else {
-                    segment_at(sw, lo, lane, W, M, maskM, halfM, sig, canon);
-                    nlo = sig + 1;
-                }
-                if (!in_part(canon, A.part, A.part_n)) {  // another pass's super-k-mer
-                    lo = nlo;
-                    continue;
-                }
-                const int n = QK ? nlo - lo : min(sig, nK - 1) - lo + 1;
-                kmers += (uint64_t)n;
-                if (WRITE && lane == 0) {
-                    // one super-k-mer: k-mers lo..lo+n-1 share the signature at
-                    // sig (binning.c:1004-1040 with the sticky window).  Span =
-                    // bases lo .. lo+n+K-2 (<= 56 for K <= 31).
-                    const uint64_t t = rbase + nseg;
-                    const uint32_t sm = (uint32_t)(window64(sw, sig) >> (64 - 2 * M));
-                    // complement wins (binning.c:1029-1040)
-                    const uint64_t rev = QK ? (qrev ? 1ull : 0ull) : (sm < halfM ? 1ull : 0ull);
-                    A.pay[3 * t + 0] = ordv | ((uint64_t)n << 32) | ((uint64_t)(sig - lo) << 38) | (rev << 44) |
-                                       ((uint64_t)lo << 45);
-                    A.pay[3 * t + 1] = window64(sw, lo);
-                    A.pay[3 * t + 2] = window64(sw, lo + 32);
-                    A.keys[t] = ((uint64_t)canon << 38) | ((uint64_t)(63 - n) << 32) | (uint32_t)t;
-                }
-                nseg++;
-                lo = nlo;
-            }
-        }
-        if (!WRITE && lane == 0) A.seg_count[r] = nseg;
-    }
-    if (!WRITE) {
-        __shared__ uint64_t sh[4];
-        const uint64_t tot = block_sum256((uint64_t)(lane == 0 ? kmers : 0), sh);
-        if (threadIdx.x == 0) A.n_kmers[blockIdx.x] = tot;
-    }
-}
-
-// map a call ordinal to the caller's read id
-DEV int32_t id_of(uint32_t ord, const int32_t* read_ids, uint32_t id_off) {
-    return read_ids ? read_ids[ord] : (int32_t)(ord + id_off);
-}
-
-
-// one record into a destination region: the binned layout (ordinal) or the
-// routed one (read id), see SkScanArgs; then rw - 1 span words from base lo
-// (n + K - 1 <= 2K - M bases: 2 words for K <= 31, 4 for K <= 63)
-DEV void put_record(const SkScanArgs& A, uint64_t* o, uint32_t ord, uint64_t lo, uint64_t n, uint64_t so,
-                    uint64_t rev, const uint64_t* sw, uint32_t sub = 0) {
-    if (A.binned_fmt) {
-        o[0] = (uint64_t)ord | (n << 32) | (so << 38) | (rev << 44) | (lo << 45);
-    } else {
-        const uint32_t id = (uint32_t)id_of(ord, A.read_ids, A.id_off);
-        o[0] = (uint64_t)id | (lo << 32) | (n << 48) | (so << 54) | (rev << ROUTED_REV_BIT);
-    }
-    for (int w = 1; w < A.rw; w++) {
-        uint64_t x = window64(sw, (int)lo + 32 * (w - 1));
-        if (A.sub_stamp && w + 1 == A.rw) x = (x & ~SUB_MASK) | sub;  // (a bucket record's sub-bin, sub_room)
-        o[w] = x;
-    }
-}
-
-// The pieces of one record bound for destination regions: its owner rank or
-// local bucket, or -- a split mmer's record -- its context sub-bin's bucket,
-// cut in two (the first ne k-mers, the edge, then the rest) when its first
-// k-mers lie in the edge.  row: the read's LDS row (the context bases).
-// Returns the number of pieces; d[] their regions.
-DEV uint32_t record_pieces(const SkScanArgs& A, uint32_t canon, int lo, int n, int so, bool rev,
-                           const uint64_t* row, uint32_t (&d)[2], uint32_t (&sub)[2], int& ne) {
-    ne = 0;
-    sub[0] = sub[1] = 0;
-    if (!A.bucket_map || !bm_has_entry(canon, A.M)) {
-        d[0] = A.owner_map && bm_has_entry(canon, A.M) ? (uint32_t)A.owner_map[canon - (1u << (2 * A.M - 1))]
-                                                       : dest_of(canon, A.G, A.dest_salt);
-        return 1;
-    }
-    const uint32_t me = A.bucket_map[canon - (1u << (2 * A.M - 1))];
-    const uint32_t b = bm_depth(me);
-    if (!b) {
-        d[0] = me & 1023u;
-        return 1;
-    }
-    const uint64_t w = window64(row, lo + so + A.M);  // the read's bases after the signature
-    const int e = sub_edge(so, n, A.K, A.M, b);
-    if (e > 0 && e < n) {
-        ne = e;
-        sub[1] = sub_ctx(so - e, A.K, A.M, b, w, rev);
-        d[0] = bm_bucket(me, A.sub_map, 0u);
-        d[1] = bm_bucket(me, A.sub_map, sub[1]);
-        return 2;
-    }
-    sub[0] = sub_ctx(so, A.K, A.M, b, w, rev);
-    d[0] = bm_bucket(me, A.sub_map, sub[0]);
-    return 1;
-}
-
-// The record pass's count loop plans each staged record once -- its pieces'
-// destinations from the map entry me (bucket_map[canon - 2^(2M-1)], loaded by
-// the caller) -- and caches the plan in the staged entry, so the placement
-// loop repeats no map lookups.  Staged entry bits: lo 0..15 (< 512 for the
-// thread kernel's reads), n 16..21, so 22..27, rev 28, row 29..37, canon
-// 38..63; planned: canon -> d0 | d1 << 10 | ne << 20 | (pieces - 1) << 25, and
-// the sub-bin depth b in bits 9..11.
-DEV uint64_t record_plan(const SkScanArgs& A, uint64_t e, uint32_t me, const uint64_t* row) {
-    const uint32_t canon = (uint32_t)(e >> 38);
-    const int lo = (int)(e & 0x1FFu), n = (int)((e >> 16) & 63u), so = (int)((e >> 22) & 63u);
-    const bool rev = ((e >> 28) & 1u) != 0;
-    uint32_t d0 = 0, d1 = 0, b = 0, two = 0;
-    int ne = 0;
-    if (!A.bucket_map || !bm_has_entry(canon, A.M)) {  // (me: not loaded for such a code)
-        d0 = A.owner_map && bm_has_entry(canon, A.M) ? (uint32_t)A.owner_map[canon - (1u << (2 * A.M - 1))]
-                                                     : dest_of(canon, A.G, A.dest_salt);
-    } else if (!(b = bm_depth(me))) {
-        d0 = me & 1023u;
-    } else {
-        const uint64_t w = window64(row, lo + so + A.M);  // the read's bases after the signature
-        const int ec = sub_edge(so, n, A.K, A.M, b);
-        if (ec > 0 && ec < n) {
-            ne = ec;
-            two = 1;
-            d0 = bm_bucket(me, A.sub_map, 0u);
-            d1 = bm_bucket(me, A.sub_map, sub_ctx(so - ec, A.K, A.M, b, w, rev));
-        } else {
-            d0 = bm_bucket(me, A.sub_map, sub_ctx(so, A.K, A.M, b, w, rev));
-        }
-    }
-    const uint64_t pk = (uint64_t)d0 | ((uint64_t)d1 << 10) | ((uint64_t)ne << 20) | ((uint64_t)two << 25);
-    return (e & 0x3FFFFF01FFull) | ((uint64_t)b << 9) | (pk << 38);
-}
-
-// Add one record to a packed 16-bit LDS destination count (two per word) and
-// return the count before it, aggregated over the wave: lanes bound for the
-// same destination share one atomic (the lowest lane's) and take their
-// offsets from the ballot.  With few destinations (ranks) every lane of a wave
-// would otherwise hit the same word and the LDS would serialise 64 returning
-// atomics per instruction (1.97 ms vs 0.27 ms for the pass at one rank).
-DEV uint32_t wave_dest_add(uint32_t* cnt2, uint32_t d) {
-    const int lane = (int)(threadIdx.x & 63u);
-    uint32_t off = 0;
-    bool pending = true;
-    for (;;) {
-        const uint64_t rem = __ballot(pending);
-        if (!rem) break;
-        const int leader = __builtin_ctzll(rem);
-        const uint32_t ld = (uint32_t)__shfl((int)d, leader, 64);
-        const bool mine = pending && d == ld;
-        const uint64_t m = __ballot(mine);
-        uint32_t b = 0;
-        if (lane == leader) {
-            const uint32_t sh = 16u * (ld & 1u);
-            b = (atomicAdd(&cnt2[ld >> 1], (uint32_t)__popcll(m) << sh) >> sh) & 0xFFFFu;
-        }
-        b = (uint32_t)__shfl((int)b, leader, 64);
-        if (mine) {
-            off = b + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-            pending = false;
-        }
-    }
-    return off;
-}
-
-// LDS row of one read in sk_thread_kernel: the read's words, then zero words
-// so that every span window (up to 4 words past the first base) stays inside
-__device__ __host__ inline int sk_row_words(int RW, int rw) { return RW + (rw > 3 ? rw - 1 : 2); }
-
-// Thread-per-read variant for short reads (RW <= SK_THREAD_RW): a block
-// stages SKT reads in LDS rows and each lane walks its own read's sticky
-// chain serially.  The wave-per-read kernel above keeps 64 lanes busy on a
-// window of only K-M+1 positions; one lane per read does the same argmax
-// with no cross-lane reduction and no idle lanes.  The window of mmer scores
-// is walked with a 2-bit shift per position (two LDS reads per segment).
-// The write pass stages each record as one u64 in LDS and the block then
-// writes its (contiguous) record range with coalesced stores.
-constexpr int SK_THREAD_RW = 16;
-// staged records per block (8 B each): 256 reads of 150 bp make ~2.5 K; a
-// block past it stores the rest directly.  With the per-destination arrays
-// (16-bit counts, two per word) and the read rows the block fits four to a CU.
-constexpr int SKT = 512;              // reads (lanes) per block
-constexpr uint32_t SK_STAGE = 4992;   // (two blocks per CU)
-static_assert(SKT <= 512, "a staged record keeps its row in 9 bits");
-constexpr uint32_t SK_MAX_DEST = 1024;  // destination regions (ranks or buckets)
-
-#ifdef KB_BIN_PROF
-// record pass phases (thread 0's clock at the block's barriers, summed over
-// blocks): row loads, walk, per-destination counts + reservations, placement
-__device__ unsigned long long g_sk_prof[8];
-#define SKPROF(ph)                                        \
-    do {                                                  \
-        if (tid == 0) {                                   \
-            const unsigned long long t1_ = clock64();     \
-            atomicAdd(&g_sk_prof[ph], t1_ - skt_);        \
-            skt_ = t1_;                                   \
-        }                                                 \
-    } while (0)
-#else
-#define SKPROF(ph) do {} while (0)
-#endif
-// a value the compiler must keep in a VGPR and cannot see through
-DEV uint32_t vreg(uint32_t v) {
-    asm("" : "+v"(v));
-    return v;
-}
-
-// QK (K < 2M): the reference's incremental branch is live (binning.c:992-1021:
-// j runs K-M .. M-1, appending bases to a score it never trims, in int
-// arithmetic that wraps).  Each lane then walks its read k-mer by k-mer with
-// the reference's own state (score, rev_score, max_score, is_rev, signature),
-// and a record is a run of k-mers with one signature position -- its so, rev
-// and mmer are whatever that state says, not the window's leftmost argmax
-template <bool WRITE, bool QK = false>
-__global__ __launch_bounds__(SKT) void sk_thread_kernel(SkScanArgs A) {
-    extern __shared__ __attribute__((aligned(16))) uint64_t smem[];
-    const int RW = A.RW, K = A.K, M = A.M;
-    const int W = K - M + 1;  // <= 57 (K <= 63): mmer starts lo..lo+W-1 end inside one 64-base window pair
-    const int RS = sk_row_words(RW, A.rw);  // row stride: zero words past the read
-    const int sh = 64 - 2 * M;
-    const uint32_t maskM = (1u << (2 * M)) - 1u;
-    const uint32_t halfM = 1u << (2 * M - 1);
-    const bool one_word = K <= 31 && M <= 12;  // (scores < 2^24 keep 8 bits for the offset)
-    const uint32_t tid = threadIdx.x;
-    uint64_t* stg = smem + SKT * RS;  // WRITE: [SK_STAGE] {lo, n, so, rev, row, canon}
-    __shared__ uint32_t span_end;
-    __shared__ unsigned long long s_base;
-    __shared__ uint32_t dcnt2[SK_MAX_DEST / 2];  // per-destination counts, 16 bits each (< SK_STAGE)
-    __shared__ uint32_t dbase[SK_MAX_DEST];  // reserved slot in the region (< region_cap < 2^32)
-    const bool route = WRITE && A.regions;          // records to destination regions, any order
-    const bool alloc = WRITE && (A.rec_ctr || route);  // records placed by block allocation
-    const bool rounds = alloc && !(route && A.G > 64);  // see the walk below
-    uint64_t kmers = 0;
-#ifdef KB_BIN_PROF
-    unsigned long long skt_ = clock64();
-#endif
-    for (uint64_t r0 = (uint64_t)blockIdx.x * SKT; r0 < A.n_reads; r0 += (uint64_t)gridDim.x * SKT) {
-        const uint32_t nrows = (uint32_t)min<uint64_t>(SKT, A.n_reads - r0);
-        __syncthreads();
-        {
-            // (the block's reads into LDS rows, eight loads in flight per lane)
-            const uint32_t nw = nrows * (uint32_t)RW;
-            for (uint32_t i0 = tid; i0 < nw; i0 += 8u * SKT) {
-                uint64_t v[8];
-#pragma unroll
-                for (int u = 0; u < 8; u++) {
-                    const uint32_t i = i0 + (uint32_t)u * SKT;
-                    v[u] = i < nw ? A.words[r0 * RW + i] : 0ull;
-                }
-#pragma unroll
-                for (int u = 0; u < 8; u++) {
-                    const uint32_t i = i0 + (uint32_t)u * SKT;
-                    if (i >= nw) break;
-                    const uint32_t row = i / (uint32_t)RW, col = i - row * (uint32_t)RW;
-                    smem[row * RS + col] = v[u];
-                }
-            }
-        }
-        if (tid < nrows)
-            for (int w = RW; w < RS; w++) smem[tid * RS + w] = 0;
-        if (tid == 0) span_end = 0;
-        __syncthreads();
-        SKPROF(0);
-        const uint64_t bfirst = WRITE && !alloc ? A.rec_base[r0] : 0;
-        // Block allocation onto few counters (ranks, or the one record counter)
-        // runs in rounds: a walk whose record finds the stage full stops there
-        // and resumes after the block has written the stage out.  (Writing such
-        // records one by one took a global atomic per record on a few hot
-        // counters -- 256 reads of 150 bp average ~2.5 K records, so about half
-        // the blocks overflowed: 1.97 ms at one rank.)  With 1024 local buckets
-        // the per-record atomics spread out and are cheaper than a round.
-        const uint64_t r = r0 + tid;
-        const uint64_t* sw = smem + tid * RS;
-        const int nK = tid < nrows ? (int)A.lens[r] - K + 1 : 0;
-        const uint64_t rbase = WRITE && !alloc && tid < nrows ? A.rec_base[r] : 0;
-        uint32_t nseg = 0;
-        int lo = 0;
-        // (QK) the reference's walk state (QWalk), and the record it closed
-        // (kept across a stage-full round: the walk does not repeat)
-        QWalk qw;
-        int q_lo = -1, q_e = 0, q_rsig = 0;
-        bool q_rrev = false;
-        for (;;) {
-            while (lo < nK) {
-                // leftmost strict argmax of the canonical score over the window
-                int best = -1, sig = lo;
-                uint32_t bsm = 0;
-                int nlo = 0;  // the next record's first k-mer
-                if (QK) {
-                    if (q_lo != lo) {  // (a stage-full round keeps the record it closed)
-                        qw.next(sw, lo, nK, K, M, maskM, q_rsig, q_rrev, q_e);
-                        q_lo = lo;
-                    }
-                    sig = q_rsig;
-                    const uint32_t sm = qw.code(sw, sig, M, maskM);
-                    best = (int)(q_rrev ? maskM - sm : sm);  // the bin's mmer code
-                    bsm = q_rrev ? 0u : halfM;               // (rev below: bsm < halfM)
-                    nlo = q_e;
-                } else if (one_word) {
-                    // K <= 31: the window's W mmers all lie in the 64-bit word at
-                    // lo, so each score is one shift of it (no shifting chain),
-                    // and the argmax is a max over (score << 8 | 255 - offset):
-                    // larger score first, then the leftmost position.  In
-                    // 32-bit halves: position i's mmer sits at bit sh - 2i,
-                    // inside the high half for i < 17 - M, across both for
-                    // i < 16, in the low half after -- one bit-field extract
-                    // (two across), and both orientations' keys in one max3
-                    // (the complement's key is the forward key ^ maskM << 8)
-                    const uint64_t x = window64(sw, lo);
-                    const uint32_t xh = (uint32_t)(x >> 32), xl = (uint32_t)x;
-                    // (loop constants held in VGPRs: a VOP3 reads one SGPR on gfx9)
-                    const uint32_t xc = vreg(maskM << 8), w2 = vreg(2u * (uint32_t)M);
-                    const int e1 = min(W, 17 - M), e2 = min(W, 16);
-                    uint32_t bk = 0;
-                    const auto hi_at = [&](int p) {
-                        const uint32_t k =
-                            vreg((__builtin_amdgcn_ubfe(xh, (uint32_t)(sh - 32 - 2 * p), w2) << 8) | (uint32_t)(255 - p));
-                        bk = max(max(bk, k), k ^ xc);
-                    };
-                    const auto mid_at = [&](int p) {
-                        const uint32_t k = vreg(((__builtin_amdgcn_alignbit(xh, xl, (uint32_t)(sh - 2 * p)) & maskM) << 8) |
-                                                (uint32_t)(255 - p));
-                        bk = max(max(bk, k), k ^ xc);
-                    };
-                    const auto lo_at = [&](int p) {
-                        const uint32_t k =
-                            vreg((__builtin_amdgcn_ubfe(xl, (uint32_t)(sh - 2 * p), w2) << 8) | (uint32_t)(255 - p));
-                        bk = max(max(bk, k), k ^ xc);
-                    };
-                    // (unrolled by hand: the loop bounds are uniform but not constant)
-                    int p = 0;
-                    for (; p + 2 <= e1; p += 2) hi_at(p), hi_at(p + 1);
-                    if (p < e1) hi_at(p++);
-                    for (; p + 2 <= e2; p += 2) mid_at(p), mid_at(p + 1);
-                    if (p < e2) mid_at(p++);
-                    for (; p + 3 <= W; p += 3) lo_at(p), lo_at(p + 1), lo_at(p + 2);
-                    for (; p < W; p++) lo_at(p);
-                    const int i = 255 - (int)(bk & 255u);
-                    sig = lo + i;
-                    best = (int)(bk >> 8);
-                    bsm = (uint32_t)(x >> (sh - 2 * i)) & maskM;
-                } else {
-                    uint64_t x = window64(sw, lo), y = window64(sw, lo + 32);
-                    for (int p = lo; p < lo + W; p++) {
-                        const uint32_t sm = (uint32_t)(x >> sh);
-                        const int c = (int)(sm >= halfM ? sm : maskM - sm);
-                        if (c > best) {
-                            best = c;
-                            sig = p;
-                            bsm = sm;
-                        }
-                        x = (x << 2) | (y >> 62);
-                        y <<= 2;
-                    }
-                }
-                if (!QK) nlo = sig + 1;
-                const uint64_t n = QK ? (uint64_t)(nlo - lo) : (uint64_t)(min(sig, nK - 1) - lo + 1);
-                if (!in_part((uint32_t)best, A.part, A.part_n)) {  // another pass's super-k-mer
-                    lo = nlo;
-                    continue;
-                }
-                if (WRITE) {
-                    const uint64_t rev = bsm < halfM ? 1ull : 0ull;  // complement wins (binning.c:1029-1040)
-                    const uint64_t e = (uint64_t)lo | (n << 16) | ((uint64_t)(sig - lo) << 22) | (rev << 28) |
-                                       ((uint64_t)tid << 29) | ((uint64_t)(uint32_t)best << 38);
-                    // one stage slot per record: one atomic per wave (the lanes
-                    // still walking take consecutive slots) -- 512 lanes' atomics
-                    // on the one LDS word serialised every segment round
-                    uint64_t loc;
-                    if (alloc) {
-                        const uint64_t am = __ballot(1);
-                        const int lead = __builtin_ctzll(am);
-                        uint32_t wb = 0;
-                        if ((int)(tid & 63u) == lead) wb = atomicAdd(&span_end, (uint32_t)__popcll(am));
-                        wb = (uint32_t)__shfl((int)wb, lead, 64);
-                        loc = (uint64_t)wb + __builtin_amdgcn_mbcnt_hi((uint32_t)(am >> 32),
-                                                                       __builtin_amdgcn_mbcnt_lo((uint32_t)am, 0u));
-                    } else {
-                        loc = rbase + nseg - bfirst;
-                    }
-                    if (loc < SK_STAGE) {
-                        stg[loc] = e;
-                    } else if (rounds) {
-                        break;  // stage full: resume at this record in the next round
-                    } else if (route) {  // many destinations: each piece its own slot
-                        uint32_t d[2], sub[2];
-                        int ne;
-                        const uint32_t np_ = record_pieces(A, (uint32_t)best, lo, (int)n, sig - lo, rev != 0, sw, d, sub, ne);
-                        for (uint32_t q = 0; q < np_; q++) {
-                            const int cut = q ? ne : 0;
-                            const uint64_t pn = np_ == 2 && q == 0 ? (uint64_t)ne : n - (uint64_t)cut;
-                            const uint64_t i = atomicAdd(&A.dest_ctr[d[q]], 1ull);
-                            if (i < region_room(A.region_base, A.region_cap, d[q]))
-                                put_record(A, A.regions + (region_off(A.region_base, A.region_cap, d[q]) + i) * (uint64_t)A.rw,
-                                           A.ord_base + (uint32_t)r, (uint64_t)(lo + cut), pn,
-                                           (uint64_t)(sig - lo - cut), rev, sw, sub[q]);
-                        }
-                    }
-                    if (loc >= SK_STAGE && !route && !alloc) {  // ordered records beyond the staging area: direct (scattered) stores
-                        const uint64_t t = rbase + nseg;
-                        A.pay[3 * t + 0] = (uint64_t)(A.ord_base + (uint32_t)r) | (n << 32) |
-                                           ((uint64_t)(sig - lo) << 38) | (rev << 44) | ((uint64_t)lo << 45);
-                        A.pay[3 * t + 1] = window64(sw, lo);
-                        A.pay[3 * t + 2] = window64(sw, lo + 32);
-                        A.keys[t] = ((uint64_t)(uint32_t)best << 38) | ((63ull - n) << 32) | (uint32_t)t;
-                    }
-                }
-                kmers += n;
-                nseg++;
-                lo = nlo;
-            }
-            if (!WRITE && tid < nrows) A.seg_count[r] = nseg;
-            if (WRITE && !alloc && nseg)
-                atomicMax(&span_end, (uint32_t)min<uint64_t>(rbase + nseg - bfirst, SK_STAGE));
-            if (!WRITE) break;
-            __syncthreads();
-            SKPROF(1);
-            const uint32_t span = min(span_end, SK_STAGE);
-            if (route) {
-                // per destination: count, reserve a range, place (LDS cursors)
-                for (uint32_t d = tid; d < (A.G + 1) / 2; d += SKT) dcnt2[d] = 0;
-                __syncthreads();
-                const bool agg = A.G <= 64;  // ranks, not local buckets: aggregate per wave
-                const uint32_t half = 1u << (2 * M - 1);
-                // two records per trip: both map loads in flight together
-                for (uint32_t i0 = tid; i0 < span; i0 += 2 * SKT) {
-                    const uint32_t i1 = i0 + SKT;
-                    const bool v1 = i1 < span;
-                    const uint64_t e0 = stg[i0], e1 = v1 ? stg[i1] : e0;
-                    uint32_t me0 = 0, me1 = 0;
-                    if (A.bucket_map) {  // (codes below half: no entry, record_plan hashes them)
-                        const uint32_t c0 = (uint32_t)(e0 >> 38), c1 = (uint32_t)(e1 >> 38);
-                        me0 = c0 >= half ? A.bucket_map[c0 - half] : 0u;
-                        me1 = c1 >= half ? A.bucket_map[c1 - half] : 0u;
-                    }
-                    const uint64_t p0 = record_plan(A, e0, me0, smem + ((e0 >> 29) & 0x1FFu) * RS);
-                    const uint64_t p1 = record_plan(A, e1, me1, smem + ((e1 >> 29) & 0x1FFu) * RS);
-                    stg[i0] = p0;
-                    if (v1) stg[i1] = p1;
-#pragma unroll
-                    for (int u = 0; u < 2; u++) {
-                        const uint64_t pl = u ? p1 : p0;
-                        if (u && !v1) break;
-                        const uint32_t np_ = 1u + (uint32_t)((pl >> 63) & 1u);
-                        for (uint32_t q = 0; q < np_; q++) {
-                            const uint32_t dq = (uint32_t)(pl >> (38 + 10 * q)) & 1023u;
-                            if (agg)
-                                wave_dest_add(dcnt2, dq);
-                            else
-                                atomicAdd(&dcnt2[dq >> 1], 1u << (16 * (dq & 1)));
-                        }
-                    }
-                }
-                __syncthreads();
-                for (uint32_t d = tid; d < A.G; d += SKT) {
-                    const uint32_t nd = (dcnt2[d >> 1] >> (16 * (d & 1))) & 0xFFFFu;
-                    dbase[d] = nd ? (uint32_t)min<unsigned long long>(
-                                        atomicAdd(&A.dest_ctr[d], (unsigned long long)nd), 0xFFFFFFFFull)
-                                  : 0u;
-                }
-                __syncthreads();
-                for (uint32_t d = tid; d < (A.G + 1) / 2; d += SKT) dcnt2[d] = 0;
-                __syncthreads();
-                SKPROF(2);
-                for (uint32_t i = tid; i < span; i += SKT) {
-                    const uint64_t e = stg[i];  // (planned)
-                    const uint32_t row = (uint32_t)((e >> 29) & 0x1FFu);
-                    const int lo = (int)(e & 0x1FFu), n = (int)((e >> 16) & 63u), so = (int)((e >> 22) & 63u);
-                    const bool rev = ((e >> 28) & 1u) != 0;
-                    const uint32_t b = (uint32_t)((e >> 9) & 7u), np_ = 1u + (uint32_t)((e >> 63) & 1u);
-                    const int ne = (int)((e >> 58) & 31u);
-                    const uint64_t* rw_ = smem + row * RS;
-                    // the pieces' sub-bins (the stamp), from the read's bases in LDS
-                    uint32_t sub[2] = {0u, 0u};
-                    if (A.sub_stamp && b) {
-                        const uint64_t w = window64(rw_, lo + so + M);
-                        if (np_ == 2) sub[1] = sub_ctx(so - ne, K, M, b, w, rev);
-                        else sub[0] = sub_ctx(so, K, M, b, w, rev);
-                    }
-                    for (uint32_t q = 0; q < np_; q++) {
-                        const uint32_t dq = (uint32_t)(e >> (38 + 10 * q)) & 1023u;
-                        const uint64_t slot =
-                            (uint64_t)dbase[dq] +
-                            (agg ? wave_dest_add(dcnt2, dq)
-                                 : ((atomicAdd(&dcnt2[dq >> 1], 1u << (16 * (dq & 1))) >> (16 * (dq & 1))) & 0xFFFFu));
-                        if (slot >= region_room(A.region_base, A.region_cap, dq)) continue;  // counted: the caller retries bigger
-                        const int cut = q ? ne : 0;
-                        const int pn = np_ == 2 && q == 0 ? ne : n - cut;
-                        put_record(A, A.regions + (region_off(A.region_base, A.region_cap, dq) + slot) * (uint64_t)A.rw,
-                                   A.ord_base + (uint32_t)(r0 + row), (uint64_t)(lo + cut), (uint64_t)pn,
-                                   (uint64_t)(so - cut), rev ? 1u : 0u, rw_, sub[q]);
-                    }
-                }
-            } else {
-                if (alloc) {  // the block's staged records get one contiguous range
-                    if (tid == 0) s_base = span ? atomicAdd(A.rec_ctr, (unsigned long long)span) : 0ull;
-                    __syncthreads();
-                }
-                const uint64_t tbase = alloc ? (uint64_t)s_base : bfirst;
-                for (uint32_t i = tid; i < span; i += SKT) {
-                    const uint64_t e = stg[i];
-                    const uint32_t elo = (uint32_t)(e & 0xFFFFu), row = (uint32_t)((e >> 29) & 0x1FFu);
-                    const uint64_t en = (e >> 16) & 63u, so = (e >> 22) & 63u, rev = (e >> 28) & 1u;
-                    const uint64_t* rw_ = smem + row * RS;
-                    const uint64_t t = tbase + i;
-                    A.pay[3 * t + 0] = (uint64_t)(A.ord_base + (uint32_t)(r0 + row)) | (en << 32) | (so << 38) |
-                                       (rev << 44) | ((uint64_t)elo << 45);
-                    A.pay[3 * t + 1] = window64(rw_, (int)elo);
-                    A.pay[3 * t + 2] = window64(rw_, (int)elo + 32);
-                    A.keys[t] = ((e >> 38) << 38) | ((63ull - en) << 32) | (uint32_t)t;
-                }
-            }
-            // another round while a walk stopped at the full stage
-#ifdef KB_BIN_PROF
-            __syncthreads();
-            SKPROF(3);
-#endif
-            if (!rounds || !__syncthreads_or(lo < nK)) break;
-            if (tid == 0) span_end = 0;
-            __syncthreads();
-        }
-    }
-    if (!WRITE || (alloc && (!route || A.binned_fmt))) {  // per-block k-mer sums (sk_kmers_total_kernel)
-        __shared__ unsigned long long shs;
-        if (tid == 0) shs = 0;
-        __syncthreads();
-        uint64_t w = kmers;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) w += (uint64_t)__shfl_xor((long long)w, off, 64);
-        if ((tid & 63u) == 0 && w) atomicAdd(&shs, (unsigned long long)w);
-        __syncthreads();
-        if (tid == 0) A.n_kmers[blockIdx.x] = shs;
-    }
-}
-
-uint64_t sk_blocks(uint64_t n_reads, int RW) {
-    if (!n_reads) return 0;
-    if (RW <= SK_THREAD_RW) return std::min<uint64_t>((n_reads + SKT - 1) / SKT, 8192);
-    return std::min<uint64_t>((n_reads + 3) / 4, 4096);
-}
-
-__global__ void sk_kmers_total_kernel(const unsigned long long* part, uint64_t n, unsigned long long* out) {
-    __shared__ uint64_t sh[4];
-    uint64_t v = 0;
-    for (uint64_t i = threadIdx.x; i < n; i += 256) v += part[i];
-    v = block_sum256(v, sh);
-    if (threadIdx.x == 0) *out += v;
-}
-
-hipError_t launch_sk_kmers_total(const unsigned long long* part, uint64_t n, unsigned long long* out,
-                                 hipStream_t s) {
-    if (!n) return hipSuccess;
-    hipLaunchKernelGGL(sk_kmers_total_kernel, dim3(1), dim3(256), 0, s, part, n, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_sk(const SkScanArgs& a, bool write, hipStream_t s) {
-    if (!a.n_reads) return hipSuccess;
-    const uint64_t blocks = sk_blocks(a.n_reads, a.RW);
-    if (a.RW <= SK_THREAD_RW) {
-        const size_t lds = (size_t)SKT * sk_row_words(a.RW, a.rw) * sizeof(uint64_t) +
-                           (write ? SK_STAGE * sizeof(uint64_t) : 0);
-        if (a.K < 2 * a.M) {  // (QK: the reference's incremental branch is live)
-            if (write)
-                hipLaunchKernelGGL((sk_thread_kernel<true, true>), dim3((unsigned)blocks), dim3(SKT), lds, s, a);
-            else
-                hipLaunchKernelGGL((sk_thread_kernel<false, true>), dim3((unsigned)blocks), dim3(SKT), lds, s, a);
-        } else if (write) {
-            hipLaunchKernelGGL(sk_thread_kernel<true>, dim3((unsigned)blocks), dim3(SKT), lds, s, a);
-        } else {
-            hipLaunchKernelGGL(sk_thread_kernel<false>, dim3((unsigned)blocks), dim3(SKT), lds, s, a);
-        }
-        return hipGetLastError();
-    }
-    const size_t lds = (size_t)4 * (a.RW + 2) * sizeof(uint64_t);
-    if (a.K < 2 * a.M) {  // (QK: a long read's walk on one lane of its wave)
-        if (write)
-            hipLaunchKernelGGL((sk_kernel<true, true>), dim3((unsigned)blocks), dim3(256), lds, s, a);
-        else
-            hipLaunchKernelGGL((sk_kernel<false, true>), dim3((unsigned)blocks), dim3(256), lds, s, a);
-    } else if (write) {
-        hipLaunchKernelGGL(sk_kernel<true>, dim3((unsigned)blocks), dim3(256), lds, s, a);
-    } else {
-        hipLaunchKernelGGL(sk_kernel<false>, dim3((unsigned)blocks), dim3(256), lds, s, a);
-    }
-    return hipGetLastError();
-}
-
-// records into bin order, structure of arrays (the bin kernel streams them)
-__global__ __launch_bounds__(256) void sk_gather_kernel(const uint64_t* __restrict__ keys,
-                                                        const uint64_t* __restrict__ pay, uint64_t R,
-                                                        uint64_t* __restrict__ srec) {
-    for (uint64_t k = blockIdx.x * 256ull + threadIdx.x; k < R; k += (uint64_t)gridDim.x * 256) {
-        const uint64_t t = (uint32_t)keys[k];
-        const uint64_t hd = pay[3 * t], w0 = pay[3 * t + 1];
-        reinterpret_cast<uint4*>(srec)[k] = make_uint4((uint32_t)hd, (uint32_t)(hd >> 32), (uint32_t)w0,
-                                                        (uint32_t)(w0 >> 32));  // (header, word 0) pairs
-        srec[2 * R + k] = pay[3 * t + 2];
-    }
-}
-
-hipError_t launch_sk_gather(const uint64_t* keys, const uint64_t* pay, uint64_t R, uint64_t* srec,
-                            hipStream_t s) {
-    if (!R) return hipSuccess;
-    const uint64_t blocks = std::min<uint64_t>((R + 255) / 256, 8192);
-    hipLaunchKernelGGL(sk_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, s, keys, pay, R, srec);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// routing (one process per GPU): the sender's records go to
-// owner(mmer) in the routed record format of route_kernel (kbin_kernels.hip)
-// -- header {id | i0 << 32 | n << 48 | sig_off << 54 | rev << 60}, then the
-// span words (rev: kbin_internal.h ROUTED_REV_BIT) --
-// destination-major, read order within a destination; the receiver turns
-// them back into binned records.
-// ---------------------------------------------------------------------------
-
-
-__global__ __launch_bounds__(256) void route_dest_kernel(const uint64_t* __restrict__ keys, uint64_t R,
-                                                         uint32_t G, const uint8_t* __restrict__ owner_map, int M,
-                                                         uint64_t* __restrict__ dkeys,
-                                                         unsigned long long* __restrict__ counts) {
-    __shared__ uint32_t hist[64];
-    if (threadIdx.x < 64) hist[threadIdx.x] = 0;
-    __syncthreads();
-    for (uint64_t t = blockIdx.x * 256ull + threadIdx.x; t < R; t += (uint64_t)gridDim.x * 256) {
-        const uint32_t mm = (uint32_t)(keys[t] >> 38);
-        const uint32_t d = owner_map && bm_has_entry(mm, M) ? (uint32_t)owner_map[mm - (1u << (2 * M - 1))]
-                                                            : owner_of_mmer(mm, G);
-        dkeys[t] = ((uint64_t)d << 32) | (uint32_t)t;
-        atomicAdd(&hist[d], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x < G && hist[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)hist[threadIdx.x]);
-}
-
-hipError_t launch_route_dest(const uint64_t* keys, uint64_t R, uint32_t G, const uint8_t* owner_map, int M,
-                             uint64_t* dkeys,
-                             unsigned long long* counts, hipStream_t s) {
-    if (!R) return hipSuccess;
-    if (G < 1 || G > 64) return hipErrorInvalidValue;
-    const uint64_t blocks = std::min<uint64_t>((R + 255) / 256, 2048);
-    hipLaunchKernelGGL(route_dest_kernel, dim3((unsigned)blocks), dim3(256), 0, s, keys, R, G, owner_map, M, dkeys, counts);
-    return hipGetLastError();
-}
-
-__global__ __launch_bounds__(256) void route_pack_binned_kernel(const uint64_t* __restrict__ sorted,
-                                                                const uint64_t* __restrict__ pay, uint64_t R,
-                                                                int rw, const int32_t* __restrict__ read_ids,
-                                                                uint32_t id_off, uint64_t* __restrict__ out) {
-    for (uint64_t k = blockIdx.x * 256ull + threadIdx.x; k < R; k += (uint64_t)gridDim.x * 256) {
-        const uint64_t t = (uint32_t)sorted[k];
-        const uint64_t hd = pay[3 * t];
-        const uint32_t id = (uint32_t)id_of((uint32_t)hd, read_ids, id_off);
-        const uint64_t n = (hd >> 32) & 63u, so = (hd >> 38) & 63u, lo = (hd >> 45) & 0xFFFFu, rev = (hd >> 44) & 1u;
-        uint64_t* o = out + k * (uint64_t)rw;
-        o[0] = (uint64_t)id | (lo << 32) | (n << 48) | (so << 54) | (rev << ROUTED_REV_BIT);
-        o[1] = pay[3 * t + 1];
-        if (rw >= 3) o[2] = pay[3 * t + 2];
-        for (int w = 3; w < rw; w++) o[w] = 0;  // (K <= 31 spans fit two words)
-    }
-}
-
-hipError_t launch_route_pack_binned(const uint64_t* sorted, const uint64_t* pay, uint64_t R, int rw,
-                                    const int32_t* read_ids, uint32_t id_off, uint64_t* out,
-                                    hipStream_t s) {
-    if (!R) return hipSuccess;
-    const uint64_t blocks = std::min<uint64_t>((R + 255) / 256, 8192);
-    hipLaunchKernelGGL(route_pack_binned_kernel, dim3((unsigned)blocks), dim3(256), 0, s, sorted, pay, R, rw,
-                       read_ids, id_off, out);
-    return hipGetLastError();
-}
-
-__global__ __launch_bounds__(256) void sk_convert_kernel(const uint64_t* __restrict__ recs, uint64_t n_rec,
-                                                         int rw, uint64_t off, int M, int K, uint64_t* __restrict__ pay,
-                                                         uint64_t* __restrict__ keys, uint32_t* status,
-                                                         unsigned long long* n_kmers) {
-    const uint32_t maskM = (1u << (2 * M)) - 1u;
-    bool neg = false;
-    uint64_t kmers = 0;
-    for (uint64_t k = blockIdx.x * 256ull + threadIdx.x; k < n_rec; k += (uint64_t)gridDim.x * 256) {
-        const uint64_t* r = recs + k * (uint64_t)rw;
-        const uint64_t h = r[0];
-        const uint64_t w0 = r[1], w1 = rw >= 3 ? r[2] : 0ull;
-        const uint32_t id = (uint32_t)h;
-        const uint64_t lo = (h >> 32) & 0xFFFFu, n = (h >> 48) & 63u, so = (h >> 54) & 63u;
-        const uint32_t sm = (uint32_t)(span_window(w0, w1, 0ull, 0ull, (int)so) >> (64 - 2 * M));
-        const bool rev = routed_rev(h, sm, K, M);  // complement wins (binning.c:1029-1040)
-        const uint32_t canon = rev ? maskM - sm : sm;
-        neg |= (int32_t)id < 0;
-        const uint64_t t = off + k;
-        pay[3 * t + 0] = (uint64_t)id | (n << 32) | (so << 38) | ((uint64_t)rev << 44) | (lo << 45);
-        pay[3 * t + 1] = w0;
-        pay[3 * t + 2] = w1;
-        keys[t] = ((uint64_t)canon << 38) | ((63ull - n) << 32) | (uint32_t)t;
-        kmers += n;
-    }
-    if (neg) atomicOr(status, ST_NEG_ID);
-    __shared__ uint64_t sh[4];
-    kmers = block_sum256(kmers, sh);
-    if (threadIdx.x == 0 && kmers) atomicAdd(n_kmers, (unsigned long long)kmers);
-}
-
-hipError_t launch_sk_convert(const uint64_t* recs, uint64_t n_rec, int rw, uint64_t off, int M, int K,
-                             uint64_t* pay, uint64_t* keys, uint32_t* status, unsigned long long* n_kmers,
-                             hipStream_t s) {
-    if (!n_rec) return hipSuccess;
-    const uint64_t blocks = std::min<uint64_t>((n_rec + 255) / 256, 8192);
-    hipLaunchKernelGGL(sk_convert_kernel, dim3((unsigned)blocks), dim3(256), 0, s, recs, n_rec, rw, off, M, K, pay,
-                       keys, status, n_kmers);
-    return hipGetLastError();
-}
 
 // ---------------------------------------------------------------------------
 // phase B: one workgroup per mmer bin
@@ -917,9 +60,6 @@ __device__ unsigned long long g_bin_prof[PROF_N];
 #define PROF_CNT(i, v) do {} while (0)
 #endif
 
-#ifdef KB_BIN_PROF
-#define KB_BIN_ABL  // (diagnostic builds: KB_BIN_ABLATE switches parts of bin_kernel off)
-#endif
 #ifndef KB_BIN_THREADS
 #define KB_BIN_THREADS 1024
 #endif
@@ -964,7 +104,6 @@ static_assert(sizeof(BinShared) % 16 == 0, "LDS carve must stay 16-B aligned (gu
 
 // block-wide exclusive scan of two u32 quantities packed in a u64 (each lane's
 // value < 2^32, totals < 2^32)
-DEV void lds_barrier();
 DEV uint64_t block_excl_scan_u64(uint64_t v, uint64_t* red, uint64_t& total, bool lds_only = false) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const uint64_t inc = wave_incl_scan(v, lane);
@@ -995,7 +134,7 @@ DEV uint32_t lanes_below(uint64_t m) {
 }
 
 // partition of a k-mer inside its bin (independent of the table hash)
-DEV uint32_t part_of(uint64_t code) { return (uint32_t)((code * 0x9E3779B97F4A7C15ull) >> 40); }
+DEV uint32_t part_of(uint64_t code) { return (uint32_t)((code * GOLDEN64) >> 40); }
 
 // ---- the bin table's key of a k-mer (the mmer is implied by the bin)
 //   KW = 1 (K <= 31): a = 2K-bit code + 1 (0 = empty slot)
@@ -1208,8 +347,15 @@ struct BinTable {
 // never inserted or staged.  Exact, as for the flat bins' sketch.
 constexpr uint32_t PFL_WORDS = PFL_CELLS / 16u;  // 32 KiB: 131072 two-bit cells
 // (PFL_LOAD, kbin_internal.h: at most this many distinct keys per cell)
-DEV uint32_t sk_cell(const TKey<1>& k, uint32_t cells);
-DEV uint32_t sk_cell(const TKey<2>& k, uint32_t cells);
+
+// the pre-filter's sketch cell of a key (independent of the table hash, whose
+// bucket comes from the low bits, and of the partition bits)
+DEV uint32_t sk_cell(const TKey<1>& k, uint32_t cells) {
+    return (uint32_t)(((mix64(k.a - 1ull) >> 32) * (uint64_t)cells) >> 32);
+}
+DEV uint32_t sk_cell(const TKey<2>& k, uint32_t cells) {
+    return (uint32_t)((((k.h64() >> 8) & 0xFFFFFFFFull) * (uint64_t)cells) >> 32);
+}
 
 // Expand the k-mers of the bin's records that fall in partition (p, l) and
 // hand them to f.  Records are the bin's super-k-mers, streamed from the
@@ -1465,20 +611,8 @@ constexpr uint32_t PF_BIT = 0x200u;        // flat_l0: a heavy bin sized for the
 constexpr uint32_t FSL_BIT = 0x400u;       // flat_l0: its lists written by flat_scatter_lds_kernel
 constexpr uint32_t OSPLIT_BIT = 0x800u;    // flat_l0: a split bin partitioned by minimizer offset (bin_body)
 constexpr double PF_LOAD = 0.06;           // sketch load (distinct keys / cells) the partition depth aims at
-
-// the pre-filter's sketch cell of a key (independent of the table hash, whose
-// bucket comes from the low bits, and of the partition bits)
-DEV uint32_t sk_cell(const TKey<1>& k, uint32_t cells) {
-    return (uint32_t)(((mix64(k.a - 1ull) >> 32) * (uint64_t)cells) >> 32);
-}
-DEV uint32_t sk_cell(const TKey<2>& k, uint32_t cells) {
-    return (uint32_t)((((k.h64() >> 8) & 0xFFFFFFFFull) * (uint64_t)cells) >> 32);
-}
 constexpr uint64_t M48 = (1ull << 48) - 1ull;
 
-// workgroup barrier ordering LDS accesses only (no wait for outstanding global
-// stores); the memory clobber keeps the compiler from moving memory ops across
-DEV void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 // bin_kernel's barriers that order LDS only (table, cursors, windows, shared
 // scalars): __syncthreads also waits for every outstanding global store of the
 // workgroup (the stage, the window's read ids, the entries), so a phase that
@@ -1516,13 +650,6 @@ DEV bool is_long_slot(uint32_t c) { return (c & (LONGB | PRUNED)) == LONGB; }
 // kernels.  The partition's entries [e0, e0 + n_ent) are read back densely
 // from e_cnt / e_off (this block wrote them: L2).  Not inlined: its sorting
 // registers stay out of the sweeps' allocation.
-DEV void sort_lists_lane(uint32_t* p, uint32_t n);
-// words past a list window that sort_lists_lane may read (never write): the
-// end of bin_kernel's LDS carve and lists_kernel's window are padded by it
-constexpr uint32_t LIST_READ_PAD = 32;
-template <int R>
-DEV void wave_sort_desc(uint32_t* p, uint32_t n, int lane);
-
 // (so, ss: the split stage of a light bin -- ordinals and slots -- or null:
 // the 8-B stage entries; RK with so and no ss: a ranked bin's packed 4-B
 // stage, slot + 1 << 16 | rank)
@@ -3256,13 +2383,7 @@ void bins_prof_report(hipStream_t s) {
     unsigned long long h[PROF_N];
     (void)hipStreamSynchronize(s);
     (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_bin_prof), sizeof(h));
-    {
-        unsigned long long g[8];
-        (void)hipMemcpyFromSymbol(g, HIP_SYMBOL(g_sk_prof), sizeof(g));
-        fprintf(stderr, "[sk_prof] rows=%llu walk=%llu counts=%llu place=%llu\n", g[0], g[1], g[2], g[3]);
-        unsigned long long z8[8] = {};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_sk_prof), z8, sizeof(z8));
-    }
+    sk_prof_report();
     static const char* nm[PROF_N] = {"bin records", "zero", "sweep1", "prune/entries", "sweep2/win place", "win sort", "win ids out", "flat",
                                  "partitions", "overflows", "omode-ovf(1e6*n+1e3*width+Lv)", "bins", "slowest-bin-occ", "slowest-bin-cycles",
                                  "occ", "records expanded", "rank", "long bitmaps", "bitmap set", "bitmap emit", "bin claim", "bin desc", "rank loads", "rank hist", "rank scatter", "rank stores",
@@ -3276,727 +2397,6 @@ void bins_prof_report(hipStream_t s) {
     (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bin_prof), z, sizeof(z));
 }
 #endif
-
-// ---------------------------------------------------------------------------
-// phase C: every list into reverse call order (binning.c:1061-1068 prepends,
-// so a list reads newest call first = descending ordinal), ordinals -> ids.
-// A block takes 256 consecutive entries: lists of <= 32 ids are sorted in the
-// registers of one lane, 33..256 by one wavefront in LDS, longer ones by the
-// whole block (LDS bitonic up to LIST_CAP, else chunks + merge passes).
-// ---------------------------------------------------------------------------
-constexpr int LIST_THREADS = 256;
-constexpr uint32_t LIST_CAP = 4096;   // longest list sorted in LDS in one piece (power of two)
-constexpr uint32_t LIST_SPAN = 7168;  // ids staged in LDS at once (28 KiB: 5 blocks per CU)
-constexpr uint32_t LIST_WIN = LIST_SPAN - 256 - 8;  // window of list starts: + one list <= 256, + alignment
-constexpr uint32_t WAVE_LIST_MAX = 4096;  // longest list one wavefront sorts in its registers (64 x 64)
-
-// descending bitonic sort of Pw (power of two) values in LDS by a group of G
-// lanes (G = 64: one wavefront, wave barriers; else the block)
-template <int G>
-DEV void bitonic_desc(uint32_t* a, uint32_t Pw, uint32_t r) {
-    for (uint32_t kk = 2; kk <= Pw; kk <<= 1) {
-        for (uint32_t jj = kk >> 1; jj > 0; jj >>= 1) {
-            for (uint32_t i = r; i < Pw; i += G) {
-                const uint32_t l2 = i ^ jj;
-                if (l2 > i) {
-                    const uint32_t x = a[i], y = a[l2];
-                    const bool desc = (i & kk) == 0;
-                    if (desc ? (x < y) : (x > y)) {
-                        a[i] = y;
-                        a[l2] = x;
-                    }
-                }
-            }
-            if (G == 64) wave_sync();
-            else __syncthreads();
-        }
-    }
-}
-
-// up to 256 values sorted descending by one wavefront, in registers: element
-// i = r * 64 + lane lives in v[r]; partners across lanes meet by xor-shuffle,
-// partners 64 or 128 apart are in the same lane.  In place in LDS.
-// Bitonic sort, descending, of R*64 values held by one wavefront in
-// registers, striped (value i = v[i / 64] of lane i % 64): partner distances
-// below 64 are lane shuffles, 64 and up are register pairs.  No LDS, no
-// barriers -- a wavefront sorts a list of up to 64 R ids on its own.
-template <int R>
-DEV void wave_bitonic(uint32_t (&v)[R], int lane) {
-#pragma unroll
-    for (int kk = 2; kk <= R * 64; kk <<= 1) {
-#pragma unroll
-        for (int jj = kk >> 1; jj > 0; jj >>= 1) {
-            if (jj >= 64) {
-                const int rj = jj >> 6;
-#pragma unroll
-                for (int r = 0; r < R; r++) {
-                    const int r2 = r ^ rj;
-                    if (r2 > r) {
-                        const uint32_t i = (uint32_t)(r * 64 + lane);
-                        const bool desc = (i & kk) == 0;
-                        const uint32_t x = v[r], y = v[r2];
-                        const uint32_t hi = x > y ? x : y, lo = x > y ? y : x;
-                        v[r] = desc ? hi : lo;
-                        v[r2] = desc ? lo : hi;
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < R; r++) {
-                    const uint32_t i = (uint32_t)(r * 64 + lane);
-                    const uint32_t y = (uint32_t)__shfl_xor((int)v[r], jj, 64);
-                    const bool lower = (lane & jj) == 0;
-                    const bool desc = (i & kk) == 0;
-                    const uint32_t hi = v[r] > y ? v[r] : y, lo = v[r] > y ? y : v[r];
-                    v[r] = (lower == desc) ? hi : lo;
-                }
-            }
-        }
-    }
-}
-
-// The same network for long lists with the stage loops left rolled: the
-// register-pair stages are unrolled per distance (RJ), so the code and the
-// register file stay at O(R), not O(R log^2 R).
-template <int R, int RJ>
-DEV void reg_stage(uint32_t (&v)[R], int lane, uint32_t kk) {
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const int r2 = r ^ RJ;
-        if (r2 > r) {
-            const bool desc = ((uint32_t)(r * 64 + lane) & kk) == 0;
-            const uint32_t x = v[r], y = v[r2];
-            const uint32_t hi = x > y ? x : y, lo = x > y ? y : x;
-            v[r] = desc ? hi : lo;
-            v[r2] = desc ? lo : hi;
-        }
-    }
-}
-
-template <int R>
-DEV void wave_bitonic_rolled(uint32_t (&v)[R], int lane) {
-    for (uint32_t kk = 2; kk <= R * 64; kk <<= 1) {
-        for (uint32_t jj = kk >> 1; jj > 0; jj >>= 1) {
-            if (jj >= 64) {
-                switch (jj >> 6) {
-                    case 1: if constexpr (R > 1) reg_stage<R, 1>(v, lane, kk); break;
-                    case 2: if constexpr (R > 2) reg_stage<R, 2>(v, lane, kk); break;
-                    case 4: if constexpr (R > 4) reg_stage<R, 4>(v, lane, kk); break;
-                    case 8: if constexpr (R > 8) reg_stage<R, 8>(v, lane, kk); break;
-                    case 16: if constexpr (R > 16) reg_stage<R, 16>(v, lane, kk); break;
-                    case 32: if constexpr (R > 32) reg_stage<R, 32>(v, lane, kk); break;
-                    default: break;
-                }
-            } else {
-                const bool lower = (lane & jj) == 0;
-#pragma unroll
-                for (int r = 0; r < R; r++) {
-                    const uint32_t y = (uint32_t)__shfl_xor((int)v[r], (int)jj, 64);
-                    const bool desc = ((uint32_t)(r * 64 + lane) & kk) == 0;
-                    const uint32_t hi = v[r] > y ? v[r] : y, lo = v[r] > y ? y : v[r];
-                    v[r] = (lower == desc) ? hi : lo;
-                }
-            }
-        }
-    }
-}
-
-template <int R>
-DEV void wave_sort_list_long(const uint32_t* __restrict__ src, int32_t* __restrict__ dst, uint32_t n, int lane,
-                             const int32_t* read_ids, uint32_t id_off) {
-    uint32_t v[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const uint32_t i = (uint32_t)(r * 64 + lane);
-        v[r] = i < n ? src[i] + 1u : 0u;
-    }
-    wave_bitonic_rolled<R>(v, lane);
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const uint32_t i = (uint32_t)(r * 64 + lane);
-        if (i < n) dst[i] = id_of(v[r] - 1u, read_ids, id_off);
-    }
-}
-
-// n <= 64 R values (ordinal + 1) in LDS, sorted descending in place
-template <int R>
-DEV void wave_sort_desc(uint32_t* p, uint32_t n, int lane) {
-    uint32_t v[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const uint32_t i = (uint32_t)(r * 64 + lane);
-        v[r] = i < n ? p[i] : 0u;
-    }
-    wave_bitonic<R>(v, lane);
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const uint32_t i = (uint32_t)(r * 64 + lane);
-        if (i < n) p[i] = v[r];
-    }
-}
-
-// one list of n <= 64 R call ordinals from HBM to its ids, reverse call order
-template <int R>
-DEV void wave_sort_list(const uint32_t* __restrict__ src, int32_t* __restrict__ dst, uint32_t n, int lane,
-                        const int32_t* read_ids, uint32_t id_off) {
-    uint32_t v[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const uint32_t i = (uint32_t)(r * 64 + lane);
-        v[r] = i < n ? src[i] + 1u : 0u;
-    }
-    wave_bitonic<R>(v, lane);
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const uint32_t i = (uint32_t)(r * 64 + lane);
-        if (i < n) dst[i] = id_of(v[r] - 1u, read_ids, id_off);
-    }
-}
-
-// up to 32 values (ordinal + 1) sorted descending in one lane's registers, in place
-// Batcher's odd-even merge network on NP = 2^k inputs, descending (the larger
-// of every pair to the lower index), keeping only the comparators whose upper
-// index is < N: a list of n <= N ids padded with zeros (below every id + 1)
-// keeps its pads in place, so the pruned network sorts it.  NP = 32: 191
-// comparators (the bitonic network: 240); N = 24: 132; 16: 63; 8: 19
-// (2 <= n <= N.  The loads and stores are branch-free -- a branch per
-// position saved the exec mask in an SGPR pair, and in bin_kernel those were
-// spilled to VGPR lanes: all N words are read (p[0 .. N) must lie inside the
-// LDS allocation: both callers leave LIST_READ_PAD words after their windows)
-// and the pads masked; position j >= n writes p[n - 1] instead, the stores
-// going out from the last position down, so p[n - 1] ends with its own value)
-template <int N, int NP>
-DEV void sort_net_desc(uint32_t* p, uint32_t n) {
-    uint32_t v[N];
-    const uint32_t last = n - 1u;
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-        const uint32_t x = p[j];
-        v[j] = (uint32_t)j < n ? x : 0u;
-    }
-#pragma unroll
-    for (int q = 1; q < NP; q <<= 1)
-#pragma unroll
-        for (int k = q; k >= 1; k >>= 1)
-#pragma unroll
-            for (int j = k % q; j + k < NP; j += 2 * k)
-#pragma unroll
-                for (int i = 0; i < k; i++) {
-                    const int a = i + j, b = i + j + k;
-                    if (b < N && a / (2 * q) == b / (2 * q)) {
-                        const uint32_t x = v[a], y = v[b < N ? b : 0];
-                        v[a] = x > y ? x : y;
-                        v[b < N ? b : 0] = x > y ? y : x;
-                    }
-                }
-#pragma unroll
-    for (int j = N - 1; j >= 0; j--) p[min((uint32_t)j, last)] = v[j];
-}
-
-// every lane's list of 2..32 ids (n outside that: nothing) in descending
-// order in its registers, with the smallest network that holds the wave's
-// longest such list (wave-uniform call)
-DEV void sort_lists_lane(uint32_t* p, uint32_t n) {
-    const bool me = n >= 2 && n <= 32;
-    const uint32_t m = wave_max_u32(me ? n : 0u);
-    if (m > 24) {
-        if (me) sort_net_desc<32, 32>(p, n);
-    } else if (m > 16) {
-        if (me) sort_net_desc<24, 32>(p, n);
-    } else if (m > 8) {
-        if (me) sort_net_desc<16, 16>(p, n);
-    } else if (m >= 2) {
-        if (me) sort_net_desc<8, 8>(p, n);
-    }
-}
-
-#ifdef KB_BIN_PROF
-__device__ unsigned long long g_list_prof[8];
-#define LPROF(ph)                                                  \
-    do {                                                           \
-        if (tid == 0) {                                            \
-            const unsigned long long _t = clock64();               \
-            lacc[ph] += _t - lt;                                   \
-            lt = _t;                                               \
-        }                                                          \
-    } while (0)
-#else
-#define LPROF(ph) do {} while (0)
-#endif
-
-__global__ __launch_bounds__(LIST_THREADS) __attribute__((amdgpu_waves_per_eu(5, 8))) void lists_kernel(ListArgs A) {
-#ifdef KB_BIN_PROF
-    unsigned long long lacc[8] = {};
-    unsigned long long lt = clock64();
-#endif
-    // staged chunks: ibuf = the chunk's ids (ordinal + 1); other chunks: buf =
-    // block sort space (LIST_CAP), wave windows inside
-    __shared__ uint32_t lds[LIST_SPAN + LIST_READ_PAD];  // (the pad: sort_lists_lane's reads)
-    static_assert(LIST_CAP <= LIST_SPAN, "block sort space aliases the staging area");
-    uint32_t* const ibuf = lds;
-    uint32_t* const buf = lds;
-    __shared__ uint32_t big[LIST_THREADS], mid[LIST_THREADS];
-    __shared__ uint32_t n_big, n_mid, s_long, w_lo[2], w_hi[2];
-    const uint32_t tid = threadIdx.x;
-    const int lane = tid & 63, wid = tid >> 6;
-    const uint64_t n_entries = A.totals[0];
-    // items: the bin kernels' queue (partitions whose ids took the global
-    // path, and long lists of the LDS path), else every entry in chunks of 256
-    // (an entry-capacity overflow publishes no entries, bins_final_kernel: the
-    // queued items' neighbours then have unwritten offsets -- no work at all,
-    // the host reruns the bin phase)
-    const uint64_t n_items = !n_entries ? 0ull
-                             : A.lq_items ? min<uint64_t>(*A.lq_n, A.lq_cap)
-                                          : (n_entries + LIST_THREADS - 1) / LIST_THREADS;
-    for (uint64_t it = blockIdx.x; it < n_items; it += gridDim.x) {
-        uint64_t e0;
-        uint32_t ne;
-        if (A.lq_items) {
-            const uint64_t x = A.lq_items[it];
-            e0 = x >> 16;
-            ne = (uint32_t)(x & 0xFFFFu);
-        } else {
-            e0 = it * LIST_THREADS;
-            ne = (uint32_t)min<uint64_t>(LIST_THREADS, n_entries - e0);
-        }
-        const uint64_t ob = A.e_off[e0], span = A.e_off[e0 + ne] - ob;
-        // (barriers in the staged path order LDS only: a full __syncthreads
-        // also waits for the previous window's global stores to land)
-        if (tid == 0) {
-            n_big = 0;
-            s_long = 0;
-        }
-        lds_barrier();
-        // this thread's entry; lists > 256 leave the staged windows: up to
-        // WAVE_LIST_MAX to lists_bucket_kernel, longer ones to this block below
-        const uint32_t n_me = tid < ne ? A.e_cnt[e0 + tid] : 0u;
-        const uint32_t rel = tid < ne ? (uint32_t)(A.e_off[e0 + tid] - ob) : 0u;  // < 2^32 ids per finalize
-        const bool short_me = tid < ne && n_me <= 256;
-        if (tid < ne && !short_me) {
-            if (n_me <= WAVE_LIST_MAX) A.long_q[atomicAdd(A.long_n, 1u)] = (uint32_t)(e0 + tid);
-            else big[atomicAdd(&n_big, 1u)] = tid;
-            s_long = 1;
-        }
-        lds_barrier();
-        // Staged windows: the chunk's id range cut every LIST_WIN ids; a short
-        // list belongs to the window its first id falls in, and a window stages
-        // [first start, last end) of its lists (<= LIST_WIN + 256 ids) with
-        // coalesced 16-B loads, sorts each list in LDS (<= 32: one lane's
-        // registers, 33..256: one wavefront) and writes the range back with 16-B
-        // stores.  (Ids of a long list inside the range are written back
-        // unsorted; its own kernel rewrites them later on the stream.)
-        // (the common case -- every list short, the chunk fits -- is one window)
-        const bool one = !s_long && span + 8 <= LIST_SPAN;
-        const uint32_t nw = one ? 1u : (uint32_t)((span + LIST_WIN - 1) / LIST_WIN);
-        const uint32_t wk = rel / LIST_WIN;
-        for (uint32_t k = 0; k < nw; k++) {
-            const uint32_t wb = k & 1u;  // double-buffered: a lane may still read the last window's range
-            if (tid == 0) {
-                w_lo[wb] = one ? 0u : 0xFFFFFFFFu;
-                w_hi[wb] = one ? (uint32_t)span : 0u;
-                n_mid = 0;
-            }
-            lds_barrier();
-            const bool in_w = short_me && (one || wk == k);
-            if (!one) {
-                if (in_w) {
-                    atomicMin(&w_lo[wb], rel);
-                    atomicMax(&w_hi[wb], rel + n_me);
-                }
-                lds_barrier();
-            }
-            const uint32_t lo_w = w_lo[wb], hi_w = w_hi[wb];
-            if (lo_w >= hi_w) continue;  // uniform: no short list starts here
-            LPROF(0);
-            const uint64_t base = (ob + lo_w) & ~3ull;   // staging is 16-B aligned
-            const uint32_t sh = (uint32_t)(ob + lo_w - base);  // ibuf[j] holds id base + j
-            const uint32_t nv = (sh + (hi_w - lo_w) + 3) >> 2;  // uint4 groups (<= LIST_SPAN / 4)
-            const uint4* src4 = reinterpret_cast<const uint4*>(A.ids_ord + base);
-            uint4* ib4 = reinterpret_cast<uint4*>(ibuf);
-            for (uint32_t g0 = 0; g0 < nv; g0 += 4 * LIST_THREADS) {  // 4 x 16 B in flight
-                uint4 v[4];
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const uint32_t g = g0 + q * LIST_THREADS + tid;
-                    if (g < nv) v[q] = src4[g];  // may read up to 3 ids past the range: same allocation
-                }
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const uint32_t g = g0 + q * LIST_THREADS + tid;
-                    if (g < nv) ib4[g] = make_uint4(v[q].x + 1u, v[q].y + 1u, v[q].z + 1u, v[q].w + 1u);
-                }
-            }
-            lds_barrier();
-            LPROF(1);
-            sort_lists_lane(ibuf + sh + (rel - lo_w), in_w ? n_me : 0u);
-            if (in_w && n_me > 32) mid[atomicAdd(&n_mid, 1u)] = tid;
-            lds_barrier();
-            LPROF(2);
-            const uint32_t nmid = n_mid;
-            for (uint32_t q = wid; q < nmid; q += LIST_THREADS / 64) {
-                const uint32_t n = A.e_cnt[e0 + mid[q]];
-                uint32_t* p = ibuf + sh + (uint32_t)(A.e_off[e0 + mid[q]] - ob - lo_w);
-                if (n <= 64) wave_sort_desc<1>(p, n, lane);
-                else if (n <= 128) wave_sort_desc<2>(p, n, lane);
-                else wave_sort_desc<4>(p, n, lane);
-                wave_sync();
-            }
-            lds_barrier();
-            LPROF(3);
-            {
-                // full groups as 16-B stores, the partial first/last group per id
-                const uint32_t end = sh + (hi_w - lo_w);  // ibuf index past the range
-                int4* dst4 = reinterpret_cast<int4*>(A.ids_out + base);
-                for (uint32_t g = tid; g < nv; g += LIST_THREADS) {
-                    const uint32_t j0 = g * 4;
-                    const uint4 v = ib4[g];
-                    if (j0 >= sh && j0 + 4 <= end) {
-                        dst4[g] = make_int4(id_of(v.x - 1u, A.read_ids, A.id_off), id_of(v.y - 1u, A.read_ids, A.id_off),
-                                            id_of(v.z - 1u, A.read_ids, A.id_off), id_of(v.w - 1u, A.read_ids, A.id_off));
-                    } else {
-                        const uint32_t vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                        for (int q = 0; q < 4; q++)
-                            if (j0 + q >= sh && j0 + q < end)
-                                A.ids_out[base + j0 + q] = id_of(vv[q] - 1u, A.read_ids, A.id_off);
-                    }
-                }
-            }
-            // the staging area is reused: every lane's LDS reads must be done (they
-            // fed its stores), but its global stores need not have landed -- a
-            // full __syncthreads() would wait for them (vmcnt), 36 % of the kernel
-            lds_barrier();
-            LPROF(4);
-#ifdef KB_BIN_PROF
-            if (tid == 0) lacc[5]++, lacc[6] += nmid;
-#endif
-        }
-        const uint32_t nbig = n_big;  // lists > WAVE_LIST_MAX: the whole block
-        if (nbig) {  // it rewrites ids the windows wrote: let those land first
-            __threadfence_block();
-            __syncthreads();
-        }
-        for (uint32_t q = 0; q < nbig; q++) {
-            const uint64_t ge = e0 + big[q];
-            const uint32_t n = A.e_cnt[ge];
-            const uint64_t o = A.e_off[ge];
-            if (n <= WAVE_LIST_MAX) continue;  // uniform
-            if (n <= (uint32_t)LIST_CAP) {
-                uint32_t Pw = 64;
-                while (Pw < n) Pw <<= 1;
-                for (uint32_t j = tid; j < Pw; j += LIST_THREADS) buf[j] = j < n ? A.ids_ord[o + j] + 1u : 0u;
-                __syncthreads();
-                for (uint32_t kk = 2; kk <= Pw; kk <<= 1) {
-                    for (uint32_t jj = kk >> 1; jj > 0; jj >>= 1) {
-                        for (uint32_t i = tid; i < Pw; i += LIST_THREADS) {
-                            const uint32_t l2 = i ^ jj;
-                            if (l2 > i) {
-                                const uint32_t x = buf[i], y = buf[l2];
-                                const bool desc = (i & kk) == 0;
-                                if (desc ? (x < y) : (x > y)) {
-                                    buf[i] = y;
-                                    buf[l2] = x;
-                                }
-                            }
-                        }
-                        __syncthreads();
-                    }
-                }
-                for (uint32_t j = tid; j < n; j += LIST_THREADS)
-                    A.ids_out[o + j] = id_of(buf[j] - 1u, A.read_ids, A.id_off);
-                __syncthreads();
-            } else {
-                // very long list: sort LDS-sized chunks, then merge passes
-                // through ids_out (as scratch) and ids_ord, ordinals + 1
-                const uint32_t C = (uint32_t)LIST_CAP;
-                uint32_t* src = A.ids_ord + o;
-                uint32_t* dst = reinterpret_cast<uint32_t*>(A.ids_out + o);
-                for (uint32_t c0 = 0; c0 < n; c0 += C) {
-                    const uint32_t cn = min(C, n - c0);
-                    for (uint32_t j = tid; j < C; j += LIST_THREADS) buf[j] = j < cn ? src[c0 + j] + 1u : 0u;
-                    __syncthreads();
-                    for (uint32_t kk = 2; kk <= C; kk <<= 1) {
-                        for (uint32_t jj = kk >> 1; jj > 0; jj >>= 1) {
-                            for (uint32_t i = tid; i < C; i += LIST_THREADS) {
-                                const uint32_t l2 = i ^ jj;
-                                if (l2 > i) {
-                                    const uint32_t x = buf[i], y = buf[l2];
-                                    const bool desc = (i & kk) == 0;
-                                    if (desc ? (x < y) : (x > y)) {
-                                        buf[i] = y;
-                                        buf[l2] = x;
-                                    }
-                                }
-                            }
-                            __syncthreads();
-                        }
-                    }
-                    for (uint32_t j = tid; j < cn; j += LIST_THREADS) dst[c0 + j] = buf[j];
-                    __syncthreads();
-                }
-                __threadfence_block();
-                __syncthreads();
-                // merge runs of width wd from dst into src, alternating
-                uint32_t* a = dst;
-                uint32_t* bb = src;
-                for (uint32_t wd = C; wd < n; wd <<= 1) {
-                    for (uint32_t t = tid; t < n; t += LIST_THREADS) {
-                        const uint32_t pair0 = (t / (2 * wd)) * 2 * wd;
-                        const uint32_t an = min(wd, n - pair0);
-                        const uint32_t b0 = pair0 + an, bn = b0 < n ? min(wd, n - b0) : 0u;
-                        const uint32_t d = t - pair0;
-                        uint32_t l1 = d > bn ? d - bn : 0u, h1 = min(d, an);
-                        while (l1 < h1) {
-                            const uint32_t i = (l1 + h1) >> 1;
-                            if (a[pair0 + i] >= a[b0 + d - i - 1]) l1 = i + 1; else h1 = i;
-                        }
-                        const uint32_t i = l1, j = d - l1;
-                        bb[t] = (i < an && (j >= bn || a[pair0 + i] >= a[b0 + j])) ? a[pair0 + i] : a[b0 + j];
-                    }
-                    __threadfence_block();
-                    __syncthreads();
-                    uint32_t* tmp = a;
-                    a = bb;
-                    bb = tmp;
-                }
-                // a holds the merged ordinals + 1; map into ids_out
-                if (a == dst) {  // ids_out holds them already: map in place
-                    for (uint32_t t = tid; t < n; t += LIST_THREADS)
-                        A.ids_out[o + t] = id_of(dst[t] - 1u, A.read_ids, A.id_off);
-                } else {
-                    for (uint32_t t = tid; t < n; t += LIST_THREADS)
-                        A.ids_out[o + t] = id_of(a[t] - 1u, A.read_ids, A.id_off);
-                }
-                __threadfence_block();
-                __syncthreads();
-            }
-        }
-        lds_barrier();  // (LDS only: big[], n_big and the staging area are reused)
-    }
-#ifdef KB_BIN_PROF
-    if (tid == 0)
-        for (int i = 0; i < 8; i++) atomicAdd(&g_list_prof[i], lacc[i]);
-#endif
-}
-
-#ifdef KB_BIN_PROF
-void lists_prof_report(hipStream_t s) {
-    unsigned long long h[8];
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_list_prof), sizeof(h));
-    fprintf(stderr, "[list_prof] pre=%llu load=%llu small=%llu mid=%llu store=%llu chunks=%llu mid_lists=%llu\n",
-            h[0], h[1], h[2], h[3], h[4], h[5], h[6]);
-    unsigned long long z[8] = {};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_list_prof), z, sizeof(z));
-}
-#endif
-
-// lists of 257..WAVE_LIST_MAX ids that lists_bucket_kernel passed on: one
-// wavefront per list, a full bitonic network in its registers (kept out of the
-// other list kernels, whose occupancy its 64-register lists would cap)
-__global__ __launch_bounds__(256) void lists_long_kernel(ListArgs A) {
-    const int lane = threadIdx.x & 63;
-    const uint32_t nq = A.long_n[1];
-    for (uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6); q < nq; q += gridDim.x * 4) {
-        const uint32_t e = A.long_q[A.long_cap + q];
-        const uint32_t n = A.e_cnt[e];
-        const uint64_t o = A.e_off[e];
-        const uint32_t* src = A.ids_ord + o;
-        int32_t* dst = A.ids_out + o;
-        if (n <= 512) wave_sort_list_long<8>(src, dst, n, lane, A.read_ids, A.id_off);
-        else if (n <= 1024) wave_sort_list_long<16>(src, dst, n, lane, A.read_ids, A.id_off);
-        else if (n <= 2048) wave_sort_list_long<32>(src, dst, n, lane, A.read_ids, A.id_off);
-        else wave_sort_list_long<64>(src, dst, n, lane, A.read_ids, A.id_off);
-    }
-}
-
-// Lists of 257..WAVE_LIST_MAX ids (high coverage: every true k-mer's list
-// is this long) by bucketing rather than a full sorting network.  One
-// wavefront per list: min/max of its ordinals, NB order-preserving buckets
-// over that range (an LDS histogram, a wave scan, an LDS scatter), then every
-// lane sorts its own bucket(s) of <= 64 ids in registers and writes them
-// straight to their place in the list.  About n (log2(64) + 3) wave steps
-// against the network's n log2^2(n) / 2; a list with a bucket past 64 ids
-// (clustered ordinals) is queued for the network (lists_long_kernel).
-constexpr uint32_t LB_WAVES = 4;
-constexpr uint32_t LB_SPAN = WAVE_LIST_MAX;  // ids per wave in LDS
-constexpr uint32_t LB_ILP = 16;              // loads in flight per lane
-
-// n <= 64 values in registers, sorted descending (0 pads last)
-template <int W>
-DEV void lane_sort_desc(uint32_t (&v)[W]) {
-#pragma unroll
-    for (int kk = 2; kk <= W; kk <<= 1) {
-#pragma unroll
-        for (int jj = kk >> 1; jj > 0; jj >>= 1) {
-#pragma unroll
-            for (int i = 0; i < W; i++) {
-                const int l2 = i ^ jj;
-                if (l2 > i) {
-                    const uint32_t x = v[i], y = v[l2];
-                    const bool desc = (i & kk) == 0;
-                    const bool sw = desc ? (x < y) : (x > y);
-                    v[i] = sw ? y : x;
-                    v[l2] = sw ? x : y;
-                }
-            }
-        }
-    }
-}
-
-
-// one lane's bucket buf[off, off + c) sorted ascending in place (values >= 1)
-template <int W>
-DEV void lane_bucket_sort_asc(uint32_t* buf, uint32_t off, uint32_t c) {
-    uint32_t v[W];
-#pragma unroll
-    for (int j = 0; j < W; j++) v[j] = (uint32_t)j < c ? buf[off + j] : 0u;
-    lane_sort_desc<W>(v);  // the c values first, descending
-#pragma unroll
-    for (int j = 0; j < W; j++)
-        if ((uint32_t)j < c) buf[off + c - 1u - (uint32_t)j] = v[j];
-}
-
-__global__ __launch_bounds__(LB_WAVES * 64) void lists_bucket_kernel(ListArgs A) {
-    __shared__ uint32_t sbuf[LB_WAVES][LB_SPAN];
-    __shared__ uint32_t scnt[LB_WAVES][256], scur[LB_WAVES][256];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    uint32_t* buf = sbuf[wid];
-    uint32_t* cnt = scnt[wid];
-    uint32_t* cur = scur[wid];
-    const uint32_t nq = *A.long_n;
-    for (uint32_t q = blockIdx.x * LB_WAVES + wid; q < nq; q += gridDim.x * LB_WAVES) {
-        const uint32_t e = A.long_q[q];
-        const uint32_t n = A.e_cnt[e];
-        const uint64_t o = A.e_off[e];
-        const uint32_t* src = A.ids_ord + o;
-        int32_t* dst = A.ids_out + o;
-        // three passes over the list, each with LB_ILP loads in flight per lane
-        // (one dependent load per iteration left every wave waiting on HBM)
-        uint32_t mn = 0xFFFFFFFFu, mx = 0;
-        for (uint32_t i0 = lane; i0 < n; i0 += 64u * LB_ILP) {
-            uint32_t x[LB_ILP];
-#pragma unroll
-            for (uint32_t k = 0; k < LB_ILP; k++) x[k] = i0 + 64u * k < n ? src[i0 + 64u * k] : 0u;
-#pragma unroll
-            for (uint32_t k = 0; k < LB_ILP; k++)
-                if (i0 + 64u * k < n) {
-                    mn = min(mn, x[k]);
-                    mx = max(mx, x[k]);
-                }
-        }
-        mx = wave_max_u32(mx);
-        mn = ~wave_max_u32(~mn);
-        // about 16 ids per bucket: each lane then sorts its buckets with
-        // 16- or 32-input networks (64 buckets for 4096 ids took 64-input ones)
-        const uint32_t nb = n <= 1024 ? 64u : n <= 2048 ? 128u : 256u;
-        // order-preserving bucket of an ordinal: floor((x - mn) * nb / range)
-        const float scale = (float)nb / ((float)(mx - mn) + 1.0f);
-        for (uint32_t b = lane; b < nb; b += 64) cnt[b] = 0;
-        wave_sync();
-        for (uint32_t i0 = lane; i0 < n; i0 += 64u * LB_ILP) {
-            uint32_t x[LB_ILP];
-#pragma unroll
-            for (uint32_t k = 0; k < LB_ILP; k++) x[k] = i0 + 64u * k < n ? src[i0 + 64u * k] : 0u;
-#pragma unroll
-            for (uint32_t k = 0; k < LB_ILP; k++)
-                if (i0 + 64u * k < n) atomicAdd(&cnt[min(nb - 1u, (uint32_t)((float)(x[k] - mn) * scale))], 1u);
-        }
-        wave_sync();
-        // lane l owns the npl = nb / 64 adjacent buckets from ba = npl l, so one
-        // wave scan of the per-lane totals places them all
-        const uint32_t npl = nb / 64u, ba = npl * (uint32_t)lane;
-        uint32_t c[4], tot = 0, big = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < 4; k++) {
-            c[k] = k < npl ? cnt[ba + k] : 0u;
-            tot += c[k];
-            big = max(big, c[k]);
-        }
-        big = wave_max_u32(big);
-        if (big > 64) {  // clustered ordinals: the sorting network takes the list
-            if (lane == 0) A.long_q[A.long_cap + atomicAdd(A.long_n + 1, 1u)] = e;
-            continue;
-        }
-        const uint32_t base = wave_incl_scan(tot, lane) - tot;  // ascending offsets
-        wave_sync();
-        {
-            uint32_t run = base;
-#pragma unroll
-            for (uint32_t k = 0; k < 4; k++)
-                if (k < npl) {
-                    cur[ba + k] = run;
-                    run += c[k];
-                }
-        }
-        wave_sync();
-        for (uint32_t i0 = lane; i0 < n; i0 += 64u * LB_ILP) {
-            uint32_t x[LB_ILP];
-#pragma unroll
-            for (uint32_t k = 0; k < LB_ILP; k++) x[k] = i0 + 64u * k < n ? src[i0 + 64u * k] : 0u;
-#pragma unroll
-            for (uint32_t k = 0; k < LB_ILP; k++)
-                if (i0 + 64u * k < n) {
-                    const uint32_t b = min(nb - 1u, (uint32_t)((float)(x[k] - mn) * scale));
-                    buf[atomicAdd(&cur[b], 1u)] = x[k] + 1u;
-                }
-        }
-        wave_sync();
-        // each lane sorts its buckets in place (ascending), so buf holds the
-        // whole list ascending; the wave then writes it reversed -- descending,
-        // binning.c:1065-1068 -- with coalesced stores (lanes writing their own
-        // buckets straight to HBM touched 64 lines per store instruction)
-        uint32_t a0 = base;
-#pragma unroll
-        for (uint32_t k = 0; k < 4; k++) {
-            if (k >= npl) break;  // (wave-uniform)
-            if (big <= 16)
-                lane_bucket_sort_asc<16>(buf, a0, c[k]);
-            else if (big <= 32)
-                lane_bucket_sort_asc<32>(buf, a0, c[k]);
-            else
-                lane_bucket_sort_asc<64>(buf, a0, c[k]);
-            a0 += c[k];
-        }
-        wave_sync();
-        for (uint32_t j = lane; j < n; j += 64) dst[j] = id_of(buf[n - 1u - j] - 1u, A.read_ids, A.id_off);
-        wave_sync();
-    }
-}
-
-hipError_t launch_lists(const ListArgs& a, uint64_t max_entries, hipStream_t s) {
-    uint64_t blocks = std::min<uint64_t>(std::max<uint64_t>(1, (max_entries + LIST_THREADS - 1) / LIST_THREADS), 16384);
-    // queued items / long lists of the last finalize (~0: none seen yet) size
-    // the grids: every list kernel strides over its queue
-    auto grid = [](uint64_t hint, uint64_t per_block, uint64_t full) {
-        if (hint == ~0ull) return full;
-        return std::min<uint64_t>(full, std::max<uint64_t>(16, (hint + hint / 2 + 64) / per_block));
-    };
-    if (a.lq_items) blocks = grid(a.lq_hint, 1, blocks);
-    if (!a.long_n_zeroed) {
-        hipError_t e = hipMemsetAsync(a.long_n, 0, 2 * sizeof(unsigned int), s);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(lists_kernel, dim3((unsigned)blocks), dim3(LIST_THREADS), 0, s, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(lists_bucket_kernel, dim3((unsigned)grid(a.long_hint[0], LB_WAVES, 4096)), dim3(LB_WAVES * 64), 0,
-                       s, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(lists_long_kernel, dim3((unsigned)grid(a.long_hint[1], 4, 1024)), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-// Bin processing order: descending records (longest-processing-time first
-// for the persistent blocks; a bin's cost follows its super-k-mers).  One
-// block; counting sort over 8 classes per power of two (class = log2 of the
-// count with 3 fractional bits), largest class first.
-DEV uint32_t order_class(uint32_t c) {
-    if (c < 8) return c;
-    const uint32_t msb = 31u - (uint32_t)__clz(c);
-    return msb * 8u + ((c >> (msb - 3u)) & 7u);  // <= 255
-}
 
 // ---------------------------------------------------------------------------
 // Cold-pass density estimate.  The partition depth of a bin comes from the
@@ -4046,7 +2446,7 @@ __global__ __launch_bounds__(HLL_THREADS) void hll_kernel(BinArgs A, uint64_t R,
             uint64_t hi, lo;
             sp.key(A.K, fl).code(hi, lo);
             sp.step();
-            const uint64_t h = mix64(lo ^ mix64(hi + 0x2545F4914F6CDD1Dull));
+            const uint64_t h = mix64(lo ^ mix64(hi + XSTAR64));
             const uint32_t ix = (uint32_t)(h >> (64 - HLL_LOG2));
             const uint32_t rank = (uint32_t)__builtin_clzll((h << HLL_LOG2) | (1ull << (HLL_LOG2 - 1))) + 1u;
             atomicMax(&reg[ix], rank);
@@ -4122,638 +2522,6 @@ double hll_estimate(const uint32_t* regs) {
     const double est = 0.7213 / (1.0 + 1.079 / m) * m * m / sum;
     if (est <= 2.5 * m && zeros) return m * std::log(m / zeros);  // small range: linear counting
     return est;
-}
-
-__global__ __launch_bounds__(1024) void bins_order_kernel(const uint32_t* __restrict__ bcount,
-                                                          const uint64_t* __restrict__ totals,
-                                                          uint32_t* __restrict__ order, uint64_t max_bins) {
-    constexpr uint32_t NC = 256;
-    __shared__ uint32_t hist[NC];
-    const uint32_t nbins = (uint32_t)min(totals[2], max_bins);
-    for (uint32_t i = threadIdx.x; i < NC; i += 1024) hist[i] = 0;
-    __syncthreads();
-    for (uint32_t b = threadIdx.x; b < nbins; b += 1024) atomicAdd(&hist[order_class(bcount[b])], 1u);
-    __syncthreads();
-    if (threadIdx.x == 0) {  // exclusive offsets, largest class first
-        uint32_t acc = 0;
-        for (int c = NC - 1; c >= 0; c--) {
-            const uint32_t h = hist[c];
-            hist[c] = acc;
-            acc += h;
-        }
-    }
-    __syncthreads();
-    for (uint32_t b = threadIdx.x; b < nbins; b += 1024) order[atomicAdd(&hist[order_class(bcount[b])], 1u)] = b;
-}
-
-hipError_t launch_bins_order(const uint32_t* bcount, const uint64_t* totals, uint32_t* order, uint64_t max_bins,
-                             hipStream_t s) {
-    hipLaunchKernelGGL(bins_order_kernel, dim3(1), dim3(1024), 0, s, bcount, totals, order, max_bins);
-    return hipGetLastError();
-}
-
-// one descriptor per processing slot: {bin, first record, records, mmer},
-// {occurrences, stage base lo, hi, 0}; stage bases are the exclusive prefix of
-// the occurrences in processing order (each bin's range, as the stage counter
-// handed them out before)
-__global__ __launch_bounds__(1024) void bins_desc_kernel(const uint32_t* __restrict__ order,
-                                                         const uint32_t* __restrict__ bstart,
-                                                         const uint32_t* __restrict__ bcount,
-                                                         const uint32_t* __restrict__ bmmer,
-                                                         const uint32_t* __restrict__ bocc,
-                                                         const uint64_t* __restrict__ totals, uint64_t max_bins,
-                                                         uint4* __restrict__ desc, unsigned long long* stage_ctr) {
-    __shared__ uint64_t red[16];
-    const uint32_t nbins = (uint32_t)min(totals[2], max_bins);
-    const uint32_t per = (nbins + 1023u) / 1024u, i0 = threadIdx.x * per;
-    uint64_t mine = 0;
-    for (uint32_t k = 0; k < per; k++)
-        if (i0 + k < nbins) mine += bocc[order[i0 + k]];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const uint64_t inc = wave_incl_scan(mine, lane);
-    if (lane == 63) red[wid] = inc;
-    __syncthreads();
-    uint64_t run = inc - mine;
-    for (int w = 0; w < 16; w++)
-        if (w < wid) run += red[w];
-    for (uint32_t k = 0; k < per; k++) {
-        const uint32_t i = i0 + k;
-        if (i >= nbins) break;
-        const uint32_t b = order[i];
-        const uint32_t occ = bocc[b];
-        desc[2 * (uint64_t)i] = make_uint4(b, bstart[b], bcount[b], bmmer[b]);
-        desc[2 * (uint64_t)i + 1] = make_uint4(occ, (uint32_t)run, (uint32_t)(run >> 32), 0u);
-        run += occ;
-    }
-    // bins without a count (spread runs: bocc 0) take their stage ranges from
-    // the stage counter, after every described range
-    if (threadIdx.x == 1023) *stage_ctr = run;
-}
-
-hipError_t launch_bins_desc(const uint32_t* order, const uint32_t* bstart, const uint32_t* bcount,
-                            const uint32_t* bmmer, const uint32_t* bocc, const uint64_t* totals, uint64_t max_bins,
-                            uint4* desc, unsigned long long* stage_ctr, hipStream_t s) {
-    hipLaunchKernelGGL(bins_desc_kernel, dim3(1), dim3(1024), 0, s, order, bstart, bcount, bmmer, bocc, totals,
-                       max_bins, desc, stage_ctr);
-    return hipGetLastError();
-}
-
-// bins_order_kernel and bins_desc_kernel in one launch: the class histogram,
-// the processing order (kept in LDS up to PLAN_LDS bins, else re-read from
-// `order`), then the descriptors in rounds of 1024 processing slots (a block
-// scan of the occurrences per round carries the stage base) -- coalesced
-// descriptor stores and independent gathers, where bins_desc_kernel walked
-// each thread's range of slots one dependent load after another
-constexpr uint32_t PLAN_LDS = 8192;
-__global__ __launch_bounds__(1024) void bins_plan_kernel(const uint32_t* __restrict__ bstart,
-                                                         const uint32_t* __restrict__ bcount,
-                                                         const uint32_t* __restrict__ bmmer,
-                                                         const uint32_t* __restrict__ bocc,
-                                                         const uint64_t* __restrict__ totals, uint64_t max_bins,
-                                                         uint32_t* __restrict__ order, uint4* __restrict__ desc,
-                                                         unsigned long long* stage_ctr) {
-    constexpr uint32_t NC = 256;
-    __shared__ uint32_t hist[NC];
-    __shared__ uint32_t ordl[PLAN_LDS];
-    __shared__ uint64_t red[16];
-    const uint32_t t = threadIdx.x;
-    const int lane = (int)(t & 63u), wid = (int)(t >> 6);
-    const uint32_t nbins = (uint32_t)min(totals[2], max_bins);
-    if (t < NC) hist[t] = 0;
-    __syncthreads();
-    for (uint32_t b = t; b < nbins; b += 1024) atomicAdd(&hist[order_class(bcount[b])], 1u);
-    __syncthreads();
-    // exclusive offsets, largest class first: thread t < 256 holds class 255 - t
-    {
-        const uint32_t h = t < NC ? hist[NC - 1u - t] : 0u;
-        const uint64_t inc = wave_incl_scan((uint64_t)h, lane);
-        if (lane == 63 && wid < 4) red[wid] = inc;
-        __syncthreads();
-        uint64_t wp = 0;
-        for (int w = 0; w < wid && w < 4; w++) wp += red[w];
-        if (t < NC) hist[NC - 1u - t] = (uint32_t)(wp + inc - h);
-        __syncthreads();
-    }
-    const bool in_lds = nbins <= PLAN_LDS;
-    for (uint32_t b = t; b < nbins; b += 1024) {
-        const uint32_t pos = atomicAdd(&hist[order_class(bcount[b])], 1u);
-        order[pos] = b;
-        if (in_lds) ordl[pos] = b;
-    }
-    __threadfence_block();
-    __syncthreads();
-    uint64_t carry = 0;
-    // (each round's four descriptor gathers are issued a round ahead: the
-    // rounds' scans no longer wait for their loads one after another)
-    auto gather = [&](uint32_t i, uint32_t& occ, uint4& d0) {
-        const bool v = i < nbins;
-        const uint32_t b = v ? (in_lds ? ordl[i] : order[i]) : 0u;
-        occ = v ? bocc[b] : 0u;
-        d0 = v ? make_uint4(b, bstart[b], bcount[b], bmmer[b]) : make_uint4(0u, 0u, 0u, 0u);
-    };
-    uint32_t occ_n = 0;
-    uint4 d0_n = make_uint4(0u, 0u, 0u, 0u);
-    gather(t, occ_n, d0_n);
-    for (uint32_t base = 0; base < nbins; base += 1024) {
-        const uint32_t i = base + t;
-        const bool v = i < nbins;
-        const uint32_t occ = occ_n;
-        const uint4 d0 = d0_n;
-        if (base + 1024 < nbins) gather(base + 1024 + t, occ_n, d0_n);
-        const uint64_t inc = wave_incl_scan((uint64_t)occ, lane);
-        if (lane == 63) red[wid] = inc;
-        __syncthreads();
-        uint64_t wp = 0, tot = 0;
-#pragma unroll
-        for (int w = 0; w < 16; w++) {
-            if (w < wid) wp += red[w];
-            tot += red[w];
-        }
-        const uint64_t run = carry + wp + inc - occ;
-        if (v) {
-            desc[2 * (uint64_t)i] = d0;
-            desc[2 * (uint64_t)i + 1] = make_uint4(occ, (uint32_t)run, (uint32_t)(run >> 32), 0u);
-        }
-        carry += tot;
-        __syncthreads();  // (red is the next round's)
-    }
-    // bins without a count (bocc 0) take their stage ranges from the stage
-    // counter, after every described range
-    if (t == 0) *stage_ctr = carry;
-}
-
-hipError_t launch_bins_plan(const uint32_t* bstart, const uint32_t* bcount, const uint32_t* bmmer,
-                            const uint32_t* bocc, const uint64_t* totals, uint64_t max_bins, uint32_t* order,
-                            uint4* desc, unsigned long long* stage_ctr, hipStream_t s) {
-    hipLaunchKernelGGL(bins_plan_kernel, dim3(1), dim3(1024), 0, s, bstart, bcount, bmmer, bocc, totals, max_bins,
-                       order, desc, stage_ctr);
-    return hipGetLastError();
-}
-
-__global__ __launch_bounds__(256) void bins_describe_kernel(const uint64_t* __restrict__ keys,
-                                                            const uint32_t* __restrict__ starts,
-                                                            const uint64_t* __restrict__ totals,
-                                                            uint32_t* __restrict__ bcount,
-                                                            uint32_t* __restrict__ bmmer, uint64_t max_bins) {
-    const uint64_t nbins = min(totals[2], max_bins);
-    for (uint64_t b = blockIdx.x * 256ull + threadIdx.x; b < nbins; b += (uint64_t)gridDim.x * 256) {
-        bcount[b] = starts[b + 1] - starts[b];
-        bmmer[b] = (uint32_t)(keys[starts[b]] >> 38);
-    }
-}
-
-hipError_t launch_bins_describe(const uint64_t* keys, const uint32_t* starts, const uint64_t* totals,
-                                uint32_t* bcount, uint32_t* bmmer, uint64_t max_bins, hipStream_t s) {
-    const uint64_t blocks = std::min<uint64_t>((max_bins + 255) / 256, 1024);
-    hipLaunchKernelGGL(bins_describe_kernel, dim3((unsigned)std::max<uint64_t>(blocks, 1)), dim3(256), 0, s, keys,
-                       starts, totals, bcount, bmmer, max_bins);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------
-// bucket_kernel: one workgroup per local bucket.  The bucket's records (pay
-// layout, contiguous) are read twice: pass 1 maps each record's mmer to a
-// slot of a small LDS table and counts (slot, 63 - n); a block scan turns the
-// counts into positions; pass 2 places every record (SoA) so that each bin is
-// contiguous with its longest records first.  Bins are appended to the bin
-// descriptors.  Replaces a global radix sort + gather: no random reads, one
-// bucket per workgroup.
-// ---------------------------------------------------------------------------
-#ifndef KB_BK_THREADS
-#define KB_BK_THREADS 1024  // (C2 1.784 -> 1.752 ms, profiles/r06/ab_bkt/)
-#endif
-constexpr int BK_THREADS = KB_BK_THREADS;  // (A/B builds: -DKB_BK_THREADS)
-constexpr uint32_t BK_SLOTS = 256;  // mmers per bucket (a bucket with more is reported)
-
-// a bucket's bins: key (mmer << SUB_BITS | context sub-bin) + 1 in an LDS table
-DEV int bk_slot(uint32_t* keys, uint32_t bkey, bool insert) {
-    const uint32_t k = bkey + 1u;
-    uint32_t i = (uint32_t)((mix64((uint64_t)bkey) >> 32) & (BK_SLOTS - 1));
-    for (uint32_t p = 0; p < BK_SLOTS; p++) {
-        const uint32_t v = keys[i];
-        if (v == k) return (int)i;
-        if (v == 0) {
-            if (!insert) return -1;
-            const uint32_t old = atomicCAS(&keys[i], 0u, k);
-            if (old == 0 || old == k) return (int)i;
-        }
-        i = (i + 1) & (BK_SLOTS - 1);
-    }
-    return -1;
-}
-
-// ROWS = k-mers per record rounded up to a power of two: n <= K - M + 1
-// (<= 31 for K <= 31, <= 57 for K <= 63); row ROWS - n puts longest first.
-// The bin key: canonical mmer << SUB_BITS | the piece's context sub-bin (0
-// unless the map splits the mmer; the record pass cut every piece to one side)
-template <int ROWS>
-DEV void bk_decode(uint64_t h, uint64_t a, uint64_t b, uint64_t last, const BucketArgs& A, uint32_t& bkey,
-                   uint32_t& row) {
-    const int M = A.M;
-    const uint32_t maskM = (1u << (2 * M)) - 1u;
-    const int so = (int)((h >> 38) & 63u);
-    const uint32_t sm = (uint32_t)(span_window(a, b, 0ull, 0ull, so) >> (64 - 2 * M));
-    const uint32_t canon = ((h >> 44) & 1u) ? maskM - sm : sm;
-    const uint32_t sub = A.sub ? (uint32_t)(last & SUB_MASK) : 0u;  // (stamped by the record pass)
-    bkey = (canon << SUB_BITS) | sub;
-    row = (uint32_t)ROWS - (uint32_t)((h >> 32) & 63u);
-}
-
-// SPW span words per record (2: K <= 31, 4: K <= 63)
-template <int SPW>
-__global__ __launch_bounds__(BK_THREADS) void bucket_kernel(BucketArgs A) {
-    constexpr uint32_t ROWS = SPW == 2 ? 32 : 64;
-    __shared__ uint32_t keys[BK_SLOTS];
-    __shared__ uint32_t hist[BK_SLOTS * ROWS];  // (slot, ROWS - n) counts, then cursors
-    __shared__ uint64_t red[BK_THREADS / 64];
-    __shared__ unsigned long long s_base, s_bin;
-    __shared__ uint32_t s_full;
-    __shared__ uint32_t socc[BK_SLOTS];  // occurrences (k-mers) per slot
-    const uint32_t tid = threadIdx.x, bk = blockIdx.x;
-    const uint64_t cnt = min<uint64_t>(A.bfill[bk], region_room(A.rbase, A.cap, bk));
-    constexpr int RWD = 1 + SPW;  // record words
-    const uint64_t* src = A.regions + region_off(A.rbase, A.cap, bk) * RWD;
-    for (uint32_t i = tid; i < BK_SLOTS; i += BK_THREADS) keys[i] = 0;
-    for (uint32_t i = tid; i < BK_SLOTS * ROWS; i += BK_THREADS) hist[i] = 0;
-    if (tid == 0) s_full = 0;
-    __syncthreads();
-#ifndef KB_BK_U
-#define KB_BK_U 12  // (records in flight: 4 -> 8 C2 1.809 -> 1.796 ms at 512 threads, profiles/r06/ab_bku/; 12 at 1024 threads, ab_bku3/)
-#endif
-#ifndef KB_BK_U4
-#define KB_BK_U4 4  // (C5 share 491.6 -> 489.2 ms, profiles/r06/ab_rows/)
-#endif
-    constexpr int U = SPW == 2 ? KB_BK_U : KB_BK_U4;  // records in flight per thread (A/B builds: -DKB_BK_U, -DKB_BK_U4)
-    for (uint64_t i0 = tid; i0 < cnt; i0 += U * BK_THREADS) {
-        uint64_t h[U], a[U], b[U], z[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const uint64_t i = i0 + (uint64_t)u * BK_THREADS;
-            if (i < cnt) {
-                h[u] = src[RWD * i];
-                a[u] = src[RWD * i + 1];
-                b[u] = src[RWD * i + 2];
-                z[u] = SPW == 2 ? b[u] : (A.sub ? src[RWD * i + SPW] : 0ull);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            if (i0 + (uint64_t)u * BK_THREADS >= cnt) break;
-            uint32_t bkey, row;
-            bk_decode<ROWS>(h[u], a[u], b[u], z[u], A, bkey, row);
-            const int sl = bk_slot(keys, bkey, true);
-            if (sl < 0) s_full = 1;
-            else atomicAdd(&hist[sl * ROWS + row], 1u);
-        }
-    }
-    __syncthreads();
-    if (s_full) {  // uniform
-        if (tid == 0) atomicOr(A.status, ST_BUCKET_FULL);
-        return;
-    }
-    // exclusive scan of the counters in (slot, row) order
-    constexpr uint32_t PER = BK_SLOTS * ROWS / BK_THREADS;
-    static_assert(ROWS % PER == 0, "a thread's counters lie in one slot");
-    uint32_t loc[PER];
-    uint64_t mine = 0;
-    uint32_t kmers = 0;  // this thread's slot: k-mers = records x n, n = ROWS - row
-#pragma unroll
-    for (uint32_t k = 0; k < PER; k++) {
-        loc[k] = hist[tid * PER + k];
-        mine += loc[k];
-        kmers += loc[k] * (ROWS - (tid * PER + k) % ROWS);
-    }
-    if (tid < BK_SLOTS) socc[tid] = 0;
-    __syncthreads();
-    if (kmers) atomicAdd(&socc[(tid * PER) / ROWS], kmers);
-    const int lane = tid & 63, wid = tid >> 6;
-    const uint64_t inc = wave_incl_scan(mine, lane);
-    if (lane == 63) red[wid] = inc;
-    __syncthreads();
-    uint64_t wp = 0;
-    for (int w = 0; w < wid; w++) wp += red[w];
-    uint32_t run = (uint32_t)(wp + inc - mine);
-    if (tid == 0) s_base = A.bbase[bk];  // exclusive prefix of the fills
-#pragma unroll
-    for (uint32_t k = 0; k < PER; k++) {
-        const uint32_t c = loc[k];
-        hist[tid * PER + k] = run;
-        run += c;
-    }
-    __syncthreads();
-    // count non-empty slots, reserve bin descriptors (one per bin key: an
-    // mmer, or one context sub-bin of a split mmer)
-    // (the dense index of a slot among the non-empty ones, from the waves'
-    // ballots -- a thread counting the set slots below it walked up to 255
-    // LDS words in series)
-    const bool has = tid < BK_SLOTS && keys[tid] != 0;
-    const uint64_t hb = __ballot(has);
-    __shared__ uint32_t wset[BK_SLOTS / 64];
-    if (tid < BK_SLOTS && lane == 0) wset[wid] = (uint32_t)__popcll(hb);
-    __syncthreads();
-    uint32_t nb = 0, below = (uint32_t)__popcll(hb & ((1ull << lane) - 1ull));
-#pragma unroll
-    for (int w = 0; w < (int)(BK_SLOTS / 64); w++) {
-        if (w < wid) below += wset[w];
-        nb += wset[w];
-    }
-    if (tid == 0) s_bin = nb ? atomicAdd(A.bin_ctr, (unsigned long long)nb) : 0ull;
-    __syncthreads();
-    if (has) {
-        const uint64_t bi = s_bin + below;
-        const uint32_t first = hist[tid * ROWS];
-        const uint32_t last = tid + 1 < BK_SLOTS ? hist[(tid + 1) * ROWS] : (uint32_t)cnt;
-        if (bi < A.max_bins) {
-            A.bstart[bi] = (uint32_t)s_base + first;
-            A.bcount[bi] = last - first;
-            // the mmer, and its context sub-bin above bit 16 (bin_kernel masks
-            // it off; the host learns each sub-bin's records from it)
-            A.bmmer[bi] = ((keys[tid] - 1u) >> SUB_BITS) | (((keys[tid] - 1u) & ((1u << SUB_BITS) - 1u)) << 16);
-            if (A.bocc) A.bocc[bi] = socc[tid];
-        }
-    }
-    __syncthreads();
-    const uint64_t base = s_base;
-#ifdef KB_BIN_ABL
-    if (A.ablate == 2) return;
-#endif
-    for (uint64_t i0 = tid; i0 < cnt; i0 += U * BK_THREADS) {
-        uint64_t h[U], a[U], b[U], c[U], d[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const uint64_t i = i0 + (uint64_t)u * BK_THREADS;
-            if (i < cnt) {
-                h[u] = src[RWD * i];
-                a[u] = src[RWD * i + 1];
-                b[u] = src[RWD * i + 2];
-                if constexpr (SPW == 4) {
-                    c[u] = src[RWD * i + 3];
-                    d[u] = src[RWD * i + 4];
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            if (i0 + (uint64_t)u * BK_THREADS >= cnt) break;
-            uint32_t bkey, row;
-            bk_decode<ROWS>(h[u], a[u], b[u], SPW == 2 ? b[u] : d[u], A, bkey, row);
-            const int sl = bk_slot(keys, bkey, false);
-            const uint64_t pos = base + atomicAdd(&hist[sl * ROWS + row], 1u);
-            if (A.rcap && pos >= A.rcap) continue;  // (a speculative launch's layout is too small: rerun)
-#ifdef KB_BIN_ABL
-            if (A.ablate == 1) {
-                if (pos == ~0ull) A.hdr[0] = h[u] ^ a[u] ^ b[u];  // (keeps the loads alive)
-                continue;
-            }
-#endif
-            reinterpret_cast<uint4*>(A.hdr)[pos] = make_uint4((uint32_t)h[u], (uint32_t)(h[u] >> 32), (uint32_t)a[u],
-                                                              (uint32_t)(a[u] >> 32));
-            if constexpr (SPW == 2) {
-                A.w1[pos] = b[u];
-            } else {
-                reinterpret_cast<uint4*>(A.w1)[pos] = make_uint4((uint32_t)b[u], (uint32_t)(b[u] >> 32), (uint32_t)c[u],
-                                                                 (uint32_t)(c[u] >> 32));
-                A.w3[pos] = d[u];
-            }
-        }
-    }
-}
-
-// exclusive prefix of the bucket fills (clamped to the capacity) -> bbase[NB + 1]
-__global__ __launch_bounds__(1024) void bucket_bases_kernel(const unsigned long long* __restrict__ bfill, uint64_t cap,
-                                                          const uint64_t* __restrict__ rbase, uint32_t NB,
-                                                          uint64_t* __restrict__ bbase) {
-    __shared__ uint64_t red[16];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const uint64_t v = threadIdx.x < NB ? min<uint64_t>(bfill[threadIdx.x], region_room(rbase, cap, threadIdx.x)) : 0ull;
-    const uint64_t inc = wave_incl_scan(v, lane);
-    if (lane == 63) red[wid] = inc;
-    __syncthreads();
-    uint64_t wp = 0, tot = 0;
-    for (int w = 0; w < 16; w++) {
-        if (w < wid) wp += red[w];
-        tot += red[w];
-    }
-    if (threadIdx.x < NB) bbase[threadIdx.x] = wp + inc - v;
-    if (threadIdx.x == 0) bbase[NB] = tot;
-}
-
-hipError_t launch_bucket_sort(const BucketArgs& a, uint32_t NB, hipStream_t s) {
-    if (!NB) return hipSuccess;
-    if (NB > 1024) return hipErrorInvalidValue;
-    if (!a.bases_ready)
-        hipLaunchKernelGGL(bucket_bases_kernel, dim3(1), dim3(1024), 0, s, a.bfill, a.cap, a.rbase, NB, a.bbase);
-    if (a.spw == 2)
-        hipLaunchKernelGGL(bucket_kernel<2>, dim3(NB), dim3(BK_THREADS), 0, s, a);
-    else if (a.spw == 4)
-        hipLaunchKernelGGL(bucket_kernel<4>, dim3(NB), dim3(BK_THREADS), 0, s, a);
-    else
-        return hipErrorInvalidValue;
-    return hipGetLastError();
-}
-
-// The receiver's plan for PERT records of a block trip (record k0 + j * 256 +
-// tid): the destination of its (last) piece, and of its edge piece when it is
-// cut (ne > 0 k-mers), its pay-layout header and span words.  In phases, so
-// that the record loads, then the map lookups, then the sub-bin lookups of all
-// PERT records are in flight together (one record's chain of dependent global
-// loads at a time left the kernel latency-bound).
-template <int SPW, int PERT>
-DEV void convert_plan(const uint64_t* __restrict__ recs, uint64_t n_rec, int rw, int M, uint32_t NB, int K,
-                      const uint32_t* __restrict__ bucket_map, const uint16_t* __restrict__ sub_map, uint64_t k0,
-                      uint32_t (&dst)[PERT], uint32_t (&dst2)[PERT], uint32_t (&ne)[PERT], uint32_t (&sub1)[PERT],
-                      uint64_t (&pay0)[PERT], uint64_t (&ps)[PERT][SPW], bool& neg, uint64_t& kmers) {
-    const uint32_t maskM = (1u << (2 * M)) - 1u, halfM = 1u << (2 * M - 1);
-    uint32_t canon[PERT], me[PERT];
-#pragma unroll
-    for (int j = 0; j < PERT; j++) {
-        const uint64_t k = k0 + (uint64_t)j * 256 + threadIdx.x;
-        dst[j] = 0xFFFFFFFFu;
-        ne[j] = 0;
-        sub1[j] = 0;
-        me[j] = 0;
-        if (k >= n_rec) continue;
-        const uint64_t* r = recs + k * (uint64_t)rw;
-        pay0[j] = r[0];
-#pragma unroll
-        for (int w = 0; w < SPW; w++) ps[j][w] = w + 1 < rw ? r[w + 1] : 0ull;
-    }
-#pragma unroll
-    for (int j = 0; j < PERT; j++) {
-        if (k0 + (uint64_t)j * 256 + threadIdx.x >= n_rec) continue;
-        const uint64_t h = pay0[j];
-        const uint32_t id = (uint32_t)h;
-        const uint64_t lo = (h >> 32) & 0xFFFFu, n = (h >> 48) & 63u, so = (h >> 54) & 63u;
-        // the signature (so <= 56) ends inside the first two span words
-        const uint32_t sm = (uint32_t)(span_window(ps[j][0], ps[j][1], 0ull, 0ull, (int)so) >> (64 - 2 * M));
-        const bool rev = routed_rev(h, sm, K, M);  // complement wins (binning.c:1029-1040)
-        canon[j] = rev ? maskM - sm : sm;
-        neg |= (int32_t)id < 0;
-        kmers += n;
-        pay0[j] = (uint64_t)id | (n << 32) | (so << 38) | ((uint64_t)rev << 44) | (lo << 45);
-        dst[j] = 0;
-    }
-    if (bucket_map) {
-#pragma unroll
-        for (int j = 0; j < PERT; j++)
-            // (K >= 2M: canon >= halfM by construction, the larger of a code and
-            // its complement; K < 2M passes run without a map.  The guard bounds
-            // the index whatever a received record says)
-            if (dst[j] != 0xFFFFFFFFu) me[j] = canon[j] >= halfM ? bucket_map[canon[j] - halfM] : 0u;
-#pragma unroll
-        for (int j = 0; j < PERT; j++) {
-            if (dst[j] == 0xFFFFFFFFu) continue;
-            const uint32_t b = bm_depth(me[j]);
-            if (!b) {
-                dst[j] = me[j] & 1023u;
-                continue;
-            }
-            const uint64_t h = pay0[j];
-            const int n = (int)((h >> 32) & 63u), so = (int)((h >> 38) & 63u);
-            const bool rev = ((h >> 44) & 1u) != 0;
-            const int e = sub_edge(so, n, K, M, b);
-            // the context at so + M: past the first two span words
-            // when a long (K > 31) record's first k-mers are its edge
-            const uint64_t wc = span_window(ps[j][0], ps[j][1], SPW > 2 ? ps[j][SPW > 2 ? 2 : 0] : 0ull,
-                                            SPW > 3 ? ps[j][SPW > 3 ? 3 : 0] : 0ull, so + M);
-            if (e > 0 && e < n) ne[j] = (uint32_t)e;
-            sub1[j] = sub_ctx(so - (int)ne[j], K, M, b, wc, rev);
-        }
-#pragma unroll
-        for (int j = 0; j < PERT; j++) {
-            if (dst[j] == 0xFFFFFFFFu || !(me[j] & BM_SPLIT)) continue;
-            const uint32_t off = me[j] & 0x0FFFFFFFu;
-            dst[j] = sub_map[off + sub1[j]];
-            if (ne[j]) dst2[j] = sub_map[off];
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < PERT; j++)
-            if (dst[j] != 0xFFFFFFFFu) dst[j] = dest_of(canon[j], NB, BUCKET_SALT);
-    }
-}
-
-// the 1 + SPW words of one piece of a planned record: the edge piece (its
-// first ne k-mers, same span start, sub-bin 0) or the (last) piece (k-mers
-// ne.., span from base ne, signature ne closer, its sub-bin stamped)
-template <int SPW>
-DEV void convert_piece(uint64_t h, const uint64_t (&ps)[SPW], uint32_t ne, uint32_t sub1, uint64_t stamp, bool edge,
-                       uint64_t (&o)[1 + SPW]) {
-    if (edge) {
-        o[0] = (h & ~(63ull << 32)) | ((uint64_t)ne << 32);
-#pragma unroll
-        for (int w = 0; w < SPW; w++) o[1 + w] = w + 1 == SPW ? ps[w] & ~stamp : ps[w];
-    } else if (ne) {
-        const uint64_t c = ne;
-        const uint64_t n = (h >> 32) & 63u, so = (h >> 38) & 63u, lo = (h >> 45) & 0xFFFFu;
-        o[0] = (h & 0xFFFFFFFFull) | ((n - c) << 32) | ((so - c) << 38) | (h & (1ull << 44)) | ((lo + c) << 45);
-        const uint64_t sw[4] = {ps[0], ps[1], SPW > 2 ? ps[SPW > 2 ? 2 : 0] : 0ull, SPW > 3 ? ps[SPW > 3 ? 3 : 0] : 0ull};
-#pragma unroll
-        for (int w = 0; w < SPW; w++) {
-            const uint64_t x = span_window(sw[0], sw[1], sw[2], sw[3], (int)c + 32 * w);
-            o[1 + w] = w + 1 == SPW ? (x & ~stamp) | (sub1 & stamp) : x;
-        }
-    } else {
-        o[0] = h;
-#pragma unroll
-        for (int w = 0; w < SPW; w++) o[1 + w] = w + 1 == SPW ? (ps[w] & ~stamp) | (sub1 & stamp) : ps[w];
-    }
-}
-
-// received routed records -> local bucket regions (pay layout, ordinal = id,
-// 1 + spw words); a block reserves one range per bucket for its 256 x 8
-// records.  A split mmer's record goes to its context sub-bin's bucket, cut in
-// two (edge piece first) when its first k-mers lie in the edge.
-template <int SPW>
-__global__ __launch_bounds__(256) void sk_convert_buckets_kernel(const uint64_t* __restrict__ recs, uint64_t n_rec,
-                                                                 int rw, int M, uint32_t NB, int K,
-                                                                 const uint32_t* __restrict__ bucket_map,
-                                                                 const uint16_t* __restrict__ sub_map, int sub_stamp,
-                                                                 uint64_t* __restrict__ regions, uint64_t cap,
-                                                                 const uint64_t* __restrict__ rbase,
-                                                                 unsigned long long* bfill, uint32_t* status,
-                                                                 unsigned long long* n_kmers, int diag_group) {
-    constexpr int PERT = 8;
-#ifdef KB_BIN_ABL
-    // (diagnostic builds only, KB_DIAG_CONVERT_GROUP: only the blocks of one
-    // XCD group b % 8 == 0 convert their records -- the rest are dropped,
-    // results wrong by design -- so a WRITE_SIZE pass can price cross-XCD
-    // line sharing; ADVICE r04: never in the product library)
-    if (diag_group && (blockIdx.x & 7u)) return;
-#else
-    (void)diag_group;
-#endif
-    __shared__ uint32_t cnt[SK_MAX_DEST];
-    __shared__ unsigned long long base[SK_MAX_DEST];
-    bool neg = false;
-    uint64_t kmers = 0;
-    const uint64_t stamp = sub_stamp ? SUB_MASK : 0ull;  // (a bucket record's last span word carries its sub-bin)
-    for (uint64_t k0 = (uint64_t)blockIdx.x * 256 * PERT; k0 < n_rec; k0 += (uint64_t)gridDim.x * 256 * PERT) {
-        for (uint32_t d = threadIdx.x; d < NB; d += 256) cnt[d] = 0;
-        __syncthreads();
-        uint32_t dst[PERT], dst2[PERT], ne[PERT], sub1[PERT];
-        uint64_t pay0[PERT], ps[PERT][SPW];
-        convert_plan<SPW, PERT>(recs, n_rec, rw, M, NB, K, bucket_map, sub_map, k0, dst, dst2, ne, sub1, pay0, ps,
-                                neg, kmers);
-#pragma unroll
-        for (int j = 0; j < PERT; j++) {
-            if (dst[j] == 0xFFFFFFFFu) continue;
-            atomicAdd(&cnt[dst[j]], 1u);
-            if (ne[j]) atomicAdd(&cnt[dst2[j]], 1u);
-        }
-        __syncthreads();
-        for (uint32_t d = threadIdx.x; d < NB; d += 256) {
-            base[d] = cnt[d] ? atomicAdd(&bfill[d], (unsigned long long)cnt[d]) : 0ull;
-            cnt[d] = 0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < PERT; j++) {
-            if (dst[j] == 0xFFFFFFFFu) continue;
-            uint64_t o[1 + SPW];
-            if (ne[j]) {  // the edge piece first
-                const uint64_t slot = base[dst2[j]] + atomicAdd(&cnt[dst2[j]], 1u);
-                if (slot < region_room(rbase, cap, dst2[j])) {
-                    convert_piece<SPW>(pay0[j], ps[j], ne[j], sub1[j], stamp, true, o);
-                    uint64_t* op = regions + (region_off(rbase, cap, dst2[j]) + slot) * (1 + SPW);
-#pragma unroll
-                    for (int w = 0; w <= SPW; w++) op[w] = o[w];
-                }
-            }
-            const uint64_t slot = base[dst[j]] + atomicAdd(&cnt[dst[j]], 1u);
-            if (slot >= region_room(rbase, cap, dst[j])) continue;  // counted: the caller retries bigger
-            convert_piece<SPW>(pay0[j], ps[j], ne[j], sub1[j], stamp, false, o);
-            uint64_t* op = regions + (region_off(rbase, cap, dst[j]) + slot) * (1 + SPW);
-#pragma unroll
-            for (int w = 0; w <= SPW; w++) op[w] = o[w];
-        }
-        __syncthreads();
-    }
-    if (neg) atomicOr(status, ST_NEG_ID);
-    __shared__ uint64_t sh[4];
-    kmers = block_sum256(kmers, sh);
-    if (threadIdx.x == 0 && kmers) atomicAdd(n_kmers, (unsigned long long)kmers);
-}
-
-hipError_t launch_sk_convert_buckets(const uint64_t* recs, uint64_t n_rec, int rw, int spw, int M, uint32_t NB,
-                                     int K, const uint32_t* bucket_map, const uint16_t* sub_map, int sub_stamp,
-                                     uint64_t* regions, uint64_t cap, const uint64_t* rbase, unsigned long long* bfill,
-                                     uint32_t* status, unsigned long long* n_kmers, hipStream_t s) {
-    if (!n_rec) return hipSuccess;
-    if (NB < 1 || NB > SK_MAX_DEST || (spw != 2 && spw != 4)) return hipErrorInvalidValue;
-#ifdef KB_BIN_ABL
-    static const int diag = getenv("KB_DIAG_CONVERT_GROUP") ? atoi(getenv("KB_DIAG_CONVERT_GROUP")) : 0;
-#else
-    const int diag = 0;
-#endif
-    const uint64_t blocks = std::min<uint64_t>((n_rec + 2047) / 2048, 4096);
-    if (spw == 2)
-        hipLaunchKernelGGL(sk_convert_buckets_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, s, recs, n_rec, rw, M,
-                           NB, K, bucket_map, sub_map, sub_stamp, regions, cap, rbase, bfill, status, n_kmers, diag);
-    else
-        hipLaunchKernelGGL(sk_convert_buckets_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, recs, n_rec, rw, M,
-                           NB, K, bucket_map, sub_map, sub_stamp, regions, cap, rbase, bfill, status, n_kmers, diag);
-    return hipGetLastError();
 }
 
 size_t bins_lds_bytes(uint32_t ts_log2, int KW) {
@@ -4846,136 +2614,24 @@ hipError_t launch_bins_heavy(const BinArgs& a, int KW, hipStream_t s, const BinA
     return KW == 1 ? launch_heavy_kw<1>(a, s, d_args) : launch_heavy_kw<2>(a, s, d_args);
 }
 
-__global__ void bins_final_kernel(const unsigned long long* gcount, uint64_t* e_off, uint64_t* totals,
-                                  uint64_t max_entries, const unsigned long long* flat_n,
-                                  const unsigned long long* lq_n, const unsigned long long* pstat,
-                                  const uint32_t* misc) {
-    if (pstat)  // (the finalize's stats next to the totals: one copy, kbin_internal.h)
-        for (int k = 0; k < KB_PSTAT; k++) totals[16 + k] = pstat[k];
-    if (misc)
-        for (int k = 0; k < 3; k++) totals[28 + k] = (uint64_t)misc[2 * k] | ((uint64_t)misc[2 * k + 1] << 32);
-    // (the next finalize's grid hints: published heavy / split bins, queued list items)
-    totals[12] = flat_n ? flat_n[0] : 0ull;
-    totals[13] = lq_n ? *lq_n : 0ull;
-    // on overflow the counters ran past the capacity (status says so) and the
-    // bins past it wrote nothing, so no entry range is whole: publish none (the
-    // lists kernel then has no work and the host reruns at the exact need)
-    const uint64_t ne0 = gcount[0] >> 32, ni = gcount[0] & 0xFFFFFFFFull;
-    const uint64_t ne = ne0 <= max_entries ? ne0 : 0;
-    totals[0] = ne;
-    totals[1] = ni;
-    e_off[ne] = ni;
-}
-
-__global__ __launch_bounds__(1024) void clear_kernel(ClearList l) {
-    for (int k = 0; k < l.n; k++)
-        for (uint32_t i = threadIdx.x; i < l.words[k]; i += 1024) l.p[k][i] = 0u;
-}
-
-// After the record pass: R (records), the largest bucket and the status word
-// next to N for the host's one mid-finalize copy, and the exclusive prefix of
-// the bucket fills (clamped to the capacity) -> bbase[NB + 1], which the bucket
-// ordering reads (one launch where a stats kernel and a bases kernel were two)
-__global__ __launch_bounds__(1024) void bucket_stats_kernel(const unsigned long long* __restrict__ bfill, uint32_t NB,
-                                                            const uint32_t* misc, uint64_t* totals, uint64_t cap,
-                                                            const uint64_t* __restrict__ rbase,
-                                                            uint64_t* __restrict__ bbase,
-                                                            const unsigned long long* __restrict__ kpart, uint64_t nk) {
-    __shared__ uint64_t red[16];
-    __shared__ uint32_t mxw[16];
-    const uint32_t t = threadIdx.x;
-    const int lane = (int)(t & 63u), wid = (int)(t >> 6);
-    // (the record pass's per-block k-mer sums: N, where a kernel of its own did it)
-    uint64_t ks = 0;
-    for (uint64_t i = t; i < nk; i += 1024) ks += kpart[i];
-    const uint64_t f = t < NB ? bfill[t] : 0ull;  // (NB <= 1024)
-    const uint64_t v = t < NB ? min<uint64_t>(f, region_room(rbase, cap, t)) : 0ull;
-    const uint64_t inc = wave_incl_scan(v, lane);
-    // fills < 2^32 (a region's capacity); a larger one is clamped for the max
-    const uint32_t m = wave_max_u32((uint32_t)min<uint64_t>(f, 0xFFFFFFFFull));
-    uint64_t fs = f;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        fs += (uint64_t)__shfl_xor((long long)fs, off, 64);
-        ks += (uint64_t)__shfl_xor((long long)ks, off, 64);
-    }
-    if (lane == 63) red[wid] = inc;
-    if (lane == 0) mxw[wid] = m;
-    __shared__ uint64_t fsum[16], ksum[16];
-    if (lane == 0) {
-        fsum[wid] = fs;
-        ksum[wid] = ks;
-    }
-    __syncthreads();
-    uint64_t wp = 0, tot = 0, sum = 0, kt = 0;
-    uint32_t mx = 0;
-#pragma unroll
-    for (int w = 0; w < 16; w++) {
-        if (w < wid) wp += red[w];
-        tot += red[w];
-        sum += fsum[w];
-        kt += ksum[w];
-        mx = max(mx, mxw[w]);
-    }
-    if (t < NB) bbase[t] = wp + inc - v;
-    if (t == 0) {
-        bbase[NB] = tot;
-        totals[8] += kt;
-        totals[12] = sum;
-        totals[13] = mx;
-        totals[14] = misc[0];
-    }
-}
-
-hipError_t launch_bucket_stats(const unsigned long long* bfill, uint32_t NB, const uint32_t* misc, uint64_t* totals,
-                               uint64_t cap, const uint64_t* rbase, uint64_t* bbase, const unsigned long long* kpart,
-                               uint64_t nk, hipStream_t s) {
-    if (NB > 1024) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(bucket_stats_kernel, dim3(1), dim3(1024), 0, s, bfill, NB, misc, totals, cap, rbase, bbase,
-                       kpart, nk);
-    return hipGetLastError();
-}
-
-hipError_t launch_clear(const ClearList& l, hipStream_t s) {
-    if (l.n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(clear_kernel, dim3(1), dim3(1024), 0, s, l);
-    return hipGetLastError();
-}
-
-hipError_t launch_bins_final(const unsigned long long* gcount, uint64_t* e_off, uint64_t* totals,
-                             uint64_t max_entries, const unsigned long long* flat_n, const unsigned long long* lq_n,
-                             const unsigned long long* pstat, const uint32_t* report_misc, hipStream_t s) {
-    hipLaunchKernelGGL(bins_final_kernel, dim3(1), dim3(1), 0, s, gcount, e_off, totals, max_entries, flat_n, lq_n,
-                       pstat, report_misc);
-    return hipGetLastError();
-}
-
 // The runtime resolves a kernel (and loads the code object holding it) at its
 // first launch in the process: milliseconds spread over a context's first
 // finalize.  kb_create resolves the binned path's kernels once per process and
-// device instead (hipFuncGetAttributes), with the other one-time setup.
+// device instead (hipFuncGetAttributes), with the other one-time setup.  Each
+// kernel file resolves its own (load_*_kernels, next to them).
 hipError_t load_bin_kernels() {
-    const void* k[] = {
-        (const void*)sk_thread_kernel<true>, (const void*)sk_thread_kernel<false>,
-        (const void*)sk_kmers_total_kernel, (const void*)sk_convert_buckets_kernel<2>,
-        (const void*)sk_convert_buckets_kernel<4>, (const void*)bucket_kernel<2>, (const void*)bucket_kernel<4>,
-        (const void*)bucket_bases_kernel, (const void*)bucket_stats_kernel, (const void*)bins_order_kernel,
-        (const void*)bins_desc_kernel, (const void*)bins_plan_kernel, (const void*)hll_kernel<1>, (const void*)hll_kernel<2>,
-        (const void*)hll_finish_kernel, (const void*)bin_kernel<1>, (const void*)bin_kernel<2>,
-        (const void*)bin_kernel_ranked<1>, (const void*)bin_kernel_ranked<2>,
-        (const void*)flat_count_kernel<1>, (const void*)flat_count_kernel<2>, (const void*)flat_scan_kernel,
-        (const void*)flat_scatter_kernel<1>, (const void*)flat_scatter_kernel<2>,
-        (const void*)flat_scatter_lds_kernel<1>, (const void*)flat_scatter_lds_kernel<2>,
-        (const void*)bin_parts_kernel<1>, (const void*)bin_parts_kernel<2>, (const void*)bins_final_kernel, (const void*)bin_args_kernel,
-        (const void*)lists_kernel, (const void*)lists_bucket_kernel, (const void*)lists_long_kernel,
-        (const void*)clear_kernel};
-    for (const void* f : k) {
-        hipFuncAttributes at;
-        const hipError_t e = hipFuncGetAttributes(&at, f);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    hipError_t e = load_sk_kernels();
+    if (e == hipSuccess) e = load_plan_kernels();
+    if (e == hipSuccess)
+        e = resolve_kernels(
+            {(const void*)hll_kernel<1>, (const void*)hll_kernel<2>, (const void*)hll_finish_kernel,
+             (const void*)bin_kernel<1>, (const void*)bin_kernel<2>, (const void*)bin_kernel_ranked<1>,
+             (const void*)bin_kernel_ranked<2>, (const void*)flat_count_kernel<1>, (const void*)flat_count_kernel<2>,
+             (const void*)flat_scan_kernel, (const void*)flat_scatter_kernel<1>, (const void*)flat_scatter_kernel<2>,
+             (const void*)flat_scatter_lds_kernel<1>, (const void*)flat_scatter_lds_kernel<2>,
+             (const void*)bin_parts_kernel<1>, (const void*)bin_parts_kernel<2>, (const void*)bin_args_kernel});
+    if (e == hipSuccess) e = load_lists_kernels();
+    return e;
 }
 
 }  // namespace kb
-

@@ -3,18 +3,29 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "kbin_hash.h"
+
+#ifdef KB_BIN_PROF
+#define KB_BIN_ABL  // (diagnostic builds: KB_BIN_ABLATE switches parts of bin_kernel off)
+#endif
+
 namespace kb {
 
 #define DEV __device__ __forceinline__
 
-DEV uint64_t mix64(uint64_t x) {  // splitmix64 finaliser
-    x ^= x >> 30;
-    x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27;
-    x *= 0x94d049bb133111ebull;
-    x ^= x >> 31;
-    return x;
+// a pass keeps the super-k-mers of its own mmer partition
+DEV bool in_part(uint32_t mmer, uint32_t part, uint32_t part_n) {
+    return part_n <= 1 || dest_of(mmer, part_n, PART_SALT) == part;
 }
+
+// map a call ordinal to the caller's read id
+DEV int32_t id_of(uint32_t ord, const int32_t* read_ids, uint32_t id_off) {
+    return read_ids ? read_ids[ord] : (int32_t)(ord + id_off);
+}
+
+// workgroup barrier ordering LDS accesses only (no wait for outstanding global
+// stores); the memory clobber keeps the compiler from moving memory ops across
+DEV void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 DEV int rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }
 

@@ -1,8 +1,13 @@
-// kbin_internal.h -- shared declarations between the HIP kernels
-// (kbin_kernels.hip) and the host C-ABI (kbin_api.hip).  Not installed.
+// kbin_internal.h -- declarations shared by the kernel files (kbin_kernels.hip:
+// the table engine and the common passes; kbin_sk.hip, kbin_plan.hip,
+// kbin_bins.hip, kbin_lists.hip: the binned engine; kbin_digest.hip) and the
+// host side (kbin_api.hip, kbin_group.hip): argument structs, record and map
+// layouts, launchers.  Not installed.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <initializer_list>
 
 namespace kb {
 
@@ -76,7 +81,7 @@ struct SkArgs {
     int K, M;
 };
 
-// ---- binned engine (kbin_bins.hip)
+// ---- binned engine (kbin_sk.hip, kbin_plan.hip, kbin_bins.hip, kbin_lists.hip)
 
 struct SkScanArgs {
     const uint64_t* words;
@@ -239,12 +244,13 @@ constexpr uint32_t KB_FLAT_MAX = 16384;  // partitions of one heavy bin's flat l
 // The bin kernels read BinArgs through a pointer (launch_bins): pointers loaded
 // from device memory are generic to the compiler, so every access through them
 // became a FLAT instruction -- counted in lgkmcnt as well, so each LDS wait
-// (every barrier) also waited for the global stores in flight.  In device code
-// the fields are global-address-space pointers (the layout is the host's) --
-// in kbin_bins.hip's device pass, where the bin kernels live (KB_BINS_TU): the
-// other files' host code assigns the fields from generic pointers, which the
-// device pass of those files also type-checks.
-#if defined(__HIP_DEVICE_COMPILE__) && defined(KB_BINS_TU)
+// (every barrier) also waited for the global stores in flight.  A file whose
+// kernels dereference BinArgs defines KB_BINARGS_GLOBAL before this header:
+// in its device pass the pointer fields are global-address-space pointers (the
+// layout is the host's).  Files that only fill BinArgs in must not: their
+// host code assigns the fields from generic pointers, which their device pass
+// type-checks as well.
+#if defined(__HIP_DEVICE_COMPILE__) && defined(KB_BINARGS_GLOBAL)
 #define KB_G __attribute__((address_space(1)))
 #else
 #define KB_G
@@ -437,8 +443,20 @@ hipError_t launch_bins_desc(const uint32_t* order, const uint32_t* bstart, const
 // of the mmers only) and its estimate (host): the cold pass's distinct keys
 hipError_t launch_hll(const BinArgs& a, uint64_t R, int KW, uint32_t* regs, uint32_t sample, hipStream_t s);
 double hll_estimate(const uint32_t* regs);
-// resolve the binned path's kernels (kb_create: once per process and device)
+// resolve the binned path's kernels (kb_create: once per process and device):
+// load_bin_kernels (kbin_bins.hip) its own and, through the others, each file's
 hipError_t load_bin_kernels();
+hipError_t load_sk_kernels();
+hipError_t load_plan_kernels();
+hipError_t load_lists_kernels();
+inline hipError_t resolve_kernels(std::initializer_list<const void*> kernels) {
+    for (const void* f : kernels) {
+        hipFuncAttributes at;
+        const hipError_t e = hipFuncGetAttributes(&at, f);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 // this thread's kb_last_error() message (kbin_group.hip's failures)
 void set_last_error(const char* msg);
 // distinct / occurrences from launch_hll's registers, on the device (no host
@@ -447,8 +465,6 @@ hipError_t launch_hll_finish(const uint32_t* regs, float* rho, hipStream_t s);
 hipError_t launch_bins_order(const uint32_t* bcount, const uint64_t* totals, uint32_t* order, uint64_t max_bins,
                              hipStream_t s);
 hipError_t launch_bucket_sort(const BucketArgs& a, uint32_t NB, hipStream_t s);
-uint64_t sk_bucket_salt();
-uint32_t sk_hash_dest(uint32_t mmer, uint32_t G, uint64_t salt);  // host twin of dest_of
 // radix path: bin descriptors from run starts of the sorted keys
 hipError_t launch_bins_describe(const uint64_t* keys, const uint32_t* starts, const uint64_t* totals,
                                 uint32_t* bcount, uint32_t* bmmer, uint64_t max_bins, hipStream_t s);
@@ -459,7 +475,8 @@ hipError_t launch_sk_convert_buckets(const uint64_t* recs, uint64_t n_rec, int r
                                      uint32_t* status, unsigned long long* n_kmers, hipStream_t s);
 size_t bins_lds_bytes(uint32_t ts_log2, int KW);
 #ifdef KB_BIN_PROF
-void bins_prof_report(hipStream_t s);
+void bins_prof_report(hipStream_t s);  // (with the record pass's: sk_prof_report)
+void sk_prof_report();
 void lists_prof_report(hipStream_t s);
 #endif
 hipError_t launch_digest(const uint32_t* mmer, const uint64_t* hi, const uint64_t* lo, const uint32_t* cnt,

@@ -110,7 +110,7 @@ hipError_t launch_unpack(const uint64_t* d_words, const uint32_t* d_lens, uint64
 // counter-based RNG so every run regenerates identical reads)
 // ---------------------------------------------------------------------------
 DEV uint64_t rng(uint64_t stream, uint64_t ctr) {
-    return mix64(stream * 0x9E3779B97F4A7C15ull + ctr + 0x632BE59BD9B4E019ull);
+    return mix64(stream * GOLDEN64 + ctr + 0x632BE59BD9B4E019ull);
 }
 
 __global__ __launch_bounds__(256) void generate_kernel(uint64_t* __restrict__ words,
@@ -468,15 +468,9 @@ hipError_t launch_scan_insert(const ScanArgs& a, int KW, hipStream_t s) {
 // route_kernel<false> counts records per (destination, read), dest-major, so
 // one exclusive scan gives every record its slot in a dest-major send buffer
 // in read order; route_kernel<true> writes them.
+// (owner rank and kb_set_partition membership: dest_of and in_part,
+// kbin_hash.h / kbin_device.h -- the binned engine's, by definition)
 // ---------------------------------------------------------------------------
-DEV uint32_t owner_of(uint32_t mmer, uint32_t G) {
-    return (uint32_t)((mix64((uint64_t)mmer + 0x5851F42D4C957F2Dull) >> 32) % G);
-}
-// kb_set_partition membership (= in_part, kbin_bins.hip: PART_SALT)
-DEV bool route_in_part(uint32_t mmer, uint32_t part, uint32_t part_n) {
-    return part_n <= 1 || (uint32_t)((mix64((uint64_t)mmer + 0x9E3779B97F4A7C15ull) >> 32) % part_n) == part;
-}
-
 template <bool PACK>
 __global__ __launch_bounds__(256) void route_kernel(RouteArgs A) {
     extern __shared__ __attribute__((aligned(16))) uint64_t smem[];
@@ -513,9 +507,9 @@ __global__ __launch_bounds__(256) void route_kernel(RouteArgs A) {
                 const int sig = rfl((int)(0xFFFFu - (key & 0xFFFFu)));
                 const uint32_t c = key >> 16;
                 const int n = min(sig, nK - 1) - seg_lo + 1;
-                const uint32_t dest = A.owner_map ? (uint32_t)A.owner_map[c - halfM] : owner_of(c, A.G);
+                const uint32_t dest = A.owner_map ? (uint32_t)A.owner_map[c - halfM] : dest_of(c, A.G, OWNER_SALT);
                 // another pass's super-k-mer: neither counted nor written
-                const bool mine = route_in_part(c, A.part, A.part_n);
+                const bool mine = in_part(c, A.part, A.part_n);
                 if (PACK && mine) {
                     const uint64_t pos = (uint64_t)(uint32_t)__shfl((int)run, (int)dest, 64);
                     uint64_t* rec = A.out + pos * (uint64_t)A.rec_words;

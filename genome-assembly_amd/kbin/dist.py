@@ -66,7 +66,7 @@ _OWNER_TABLES = {}
 def owner_of(mmer_code: int, n_dest: int, K: int = 31, M: int = 7, part: int = 0, n_parts: int = 1) -> int:
     """Owning rank of a mmer among n_dest ranks in pass (part, n_parts): the
     routing kernels' owner -- kb_owner_table (include/kbin.h) for a canonical
-    code at K >= 2M, the owner hash (owner_of() in csrc/kbin_kernels.hip)
+    code at K >= 2M, the owner hash (dest_of with OWNER_SALT, csrc/kbin_hash.h)
     for any other code"""
     half = 1 << (2 * M - 1)
     if K < 2 * M or not half <= mmer_code < 2 * half:

@@ -71,7 +71,8 @@ typedef struct kb_ctx kb_ctx;
 typedef struct {
     int32_t K;              /* KMER_SIZE       (binning.c:11); M <= K <= 63      */
     int32_t M;              /* MMER_SIZE       (binning.c:10); 1 <= M <= 8 (K < 2M:
-                               the live incremental branch, one GPU, binned engine) */
+                               the live incremental branch: the binned engine, any
+                               read length, routable -- complement flag in bit 60) */
     int32_t cutoff;         /* ABUNDANCE_CUTOFF (binning.c:12); >= 0            */
     int32_t max_read_len;   /* longest read accepted (READ_LENGTH-2 for fgets)  */
     int32_t device;         /* HIP device ordinal                               */

@@ -57,7 +57,7 @@ def _word(v, p):
 
 
 def _in_part(mmer: int, part: int, n_parts: int) -> bool:
-    """kb_set_partition membership (route_in_part, csrc/kbin_kernels.hip)"""
+    """kb_set_partition membership (in_part, csrc/kbin_device.h)"""
     from kbin.dist import _mix64
     return n_parts <= 1 or (_mix64(mmer + 0x9E3779B97F4A7C15) >> 32) % n_parts == part
 

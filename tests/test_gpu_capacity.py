@@ -27,7 +27,7 @@ from test_gpu_scale import _generate, _unpack
 
 pytestmark = [pytest.mark.gpu]
 
-PART_SALT = 0x9E3779B97F4A7C15  # kbin_bins.hip in_part (kb_set_partition)
+PART_SALT = 0x9E3779B97F4A7C15  # csrc/kbin_hash.h PART_SALT, kbin_device.h in_part (kb_set_partition)
 
 
 def part_mask(M, part, n_parts):

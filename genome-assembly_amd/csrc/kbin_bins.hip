@@ -1092,7 +1092,7 @@ DEV void bin_body(const BinArgs& A) {
     uint32_t* const pfl_sk = KW == 2 ? reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(ring0) +
                                                                    (size_t)BIN_WAVES * Q * (8u * KW + 6u))
                                      : nullptr;
-    const uint64_t nbins = min(A.totals[2], A.max_bins);
+    const uint64_t nbins = min(A.totals[T_BINS], A.max_bins);
     const uint32_t tid = threadIdx.x;
 #ifdef KB_BIN_PROF
     unsigned long long* const pacc = S.prof;
@@ -1127,9 +1127,9 @@ DEV void bin_body(const BinArgs& A) {
                 // items are offset-pool indices: entry e0 + p of a published
                 // bin is its partition p (the bin's last entry is no item)
                 S.item = 0xFFFFFFFFu;
-                const unsigned long long npool = A.flat_n[1];
+                const unsigned long long npool = A.flat_n[FN_POOL];
                 for (;;) {
-                    const unsigned long long it = atomicAdd(&A.flat_n[5], 1ull);
+                    const unsigned long long it = atomicAdd(&A.flat_n[FN_SWEEP], 1ull);
                     if (it >= npool) break;
                     const uint32_t fb0 = A.pool_bin[it];
                     if (fb0 == 0xFFFFFFFFu) continue;
@@ -1287,18 +1287,18 @@ DEV void bin_body(const BinArgs& A) {
             }
             // the build kernels' items: chunks of FB_CHUNK records
             const uint32_t nch = (hi - lo + FB_CHUNK - 1) / FB_CHUNK;
-            if (tid == 0) S.i0 = atomicAdd(&A.flat_n[2], (unsigned long long)nch);
+            if (tid == 0) S.i0 = atomicAdd(&A.flat_n[FN_BUILD], (unsigned long long)nch);
             __syncthreads();
             for (uint32_t k = tid; k < nch; k += BIN_THREADS) A.chunk_bin[S.i0 + k] = b;
             if (tid == 0) {
-                if (A.pstat) atomicAdd(&A.pstat[flat ? 0 : 1], 1ull);
-                if (fsl) atomicAdd(&A.flat_n[6], 1ull);  // (LDS-staged lists)
+                if (A.pstat) atomicAdd(&A.pstat[flat ? PS_HEAVY : PS_SPLIT], 1ull);
+                if (fsl) atomicAdd(&A.flat_n[FN_STAGED], 1ull);  // (LDS-staged lists)
                 A.flat_obase[b] = S.e0;
                 A.flat_sbase[b] = S.stage_base;
                 A.flat_l0[b] = l0 | (split ? SPLIT_BIT : 0u) | (pfb ? PF_BIT : 0u) | (fsl ? FSL_BIT : 0u) |
                                (osplit ? OSPLIT_BIT : 0u);
                 A.flat_chunk[b] = (uint32_t)S.i0;
-                A.flat_list[atomicAdd(A.flat_n, 1ull)] = b;
+                A.flat_list[atomicAdd(&A.flat_n[FN_BINS], 1ull)] = b;
             }
             PROF_MARK(7);
             continue;  // (the next kernel launch sees every store)
@@ -1349,7 +1349,7 @@ DEV void bin_body(const BinArgs& A) {
                     if (atomicOr(&pfl_sk[cl >> 4], bit) & bit) atomicOr(&pfl_sk[cl >> 4], bit << 1);
                 });
                 bar_lds(A);
-                if (tid == 0 && A.pstat) atomicAdd(&A.pstat[8], 1ull);
+                if (tid == 0 && A.pstat) atomicAdd(&A.pstat[PS_PF_LIGHT], 1ull);
             }
         }
         // ranked bin (long lists expected): records ranked by call ordinal,
@@ -1369,7 +1369,7 @@ DEV void bin_body(const BinArgs& A) {
                 PROF_MARK(7);
                 bin_ranks(A.hdr, A.rrank, A.rord, S, lo, hi, nl, cnt PROF_ARGS);
                 PROF_CNT(30, R);
-                if (tid == 0 && A.pstat) atomicAdd(&A.pstat[9], 1ull);
+                if (tid == 0 && A.pstat) atomicAdd(&A.pstat[PS_RANKED], 1ull);
             }
         }
         for (uint32_t p0 = p_lo; p0 < p_hi; p0++) {
@@ -1656,7 +1656,7 @@ DEV void bin_body(const BinArgs& A) {
                 PROF_CNT(9, 1);
                 PROF_CNT(10, omode ? 1000000u + (ohi - olo) * 1000u + Lv : 0u);  // (diagnostic: offset-range overflows)
                 if (tid == 0) {
-                    if (A.pstat) atomicAdd(&A.pstat[3], 1ull);
+                    if (A.pstat) atomicAdd(&A.pstat[PS_REDO], 1ull);
                     uint32_t& sp = S.spq[pq];
                     if (ts < TS) {  // a larger table first
                         S.ts = min(TS, ts << 2);
@@ -1703,17 +1703,17 @@ DEV void bin_body(const BinArgs& A) {
             const uint64_t tot = tot_s + tot_l;  // (both fields < 2^32)
             if (tid == 0) {
                 const uint32_t ne = (uint32_t)tot, ni = (uint32_t)(tot >> 32);
-                atomicAdd(&A.gcount[2], (unsigned long long)(S.n_keys + S.n_single));  // distinct before prune
+                atomicAdd(&A.gcount[G_DISTINCT], (unsigned long long)(S.n_keys + S.n_single));  // distinct before prune
                 // occurrences counted (pre-filtered singles count once each): the
                 // finalize checks the sum against the pass's k-mers
-                atomicAdd(&A.gcount[1], (unsigned long long)S.sumc + S.n_single);
+                atomicAdd(&A.gcount[G_COUNTED], (unsigned long long)S.sumc + S.n_single);
                 if (A.tab_keys) atomicAdd(A.tab_keys, (unsigned long long)S.n_keys);
                 if (A.pstat) {
-                    atomicAdd(&A.pstat[2], 1ull);
-                    atomicMax(&A.pstat[4], (unsigned long long)(Lv + (omode ? l0 : 0u)));
-                    if (S.n_single) atomicAdd(&A.pstat[5], (unsigned long long)S.n_single);
-                    if (omode) atomicAdd(&A.pstat[6], 1ull);
-                    if (PHASE == 1 && flat) atomicAdd(&A.pstat[7], 1ull);
+                    atomicAdd(&A.pstat[PS_PARTS], 1ull);
+                    atomicMax(&A.pstat[PS_DEPTH], (unsigned long long)(Lv + (omode ? l0 : 0u)));
+                    if (S.n_single) atomicAdd(&A.pstat[PS_PREFILTERED], (unsigned long long)S.n_single);
+                    if (omode) atomicAdd(&A.pstat[PS_OFFSET], 1ull);
+                    if (PHASE == 1 && flat) atomicAdd(&A.pstat[PS_FLAT], 1ull);
                 }
                 // entries and ids from ONE packed counter (entries << 32 | ids; both
                 // totals < 2^32): consecutive entries own consecutive id ranges,
@@ -1723,8 +1723,8 @@ DEV void bin_body(const BinArgs& A) {
                     // (diagnostic: the price of this returning device-scope
                     // atomic on the partition's critical path -- a second one
                     // in series before it, results unchanged)
-                    const unsigned long long d = atomicAdd(&A.gcount[2], 0ull);
-                    const unsigned long long got = tot ? atomicAdd(&A.gcount[0] + (d == ~0ull ? 1 : 0),
+                    const unsigned long long d = atomicAdd(&A.gcount[G_DISTINCT], 0ull);
+                    const unsigned long long got = tot ? atomicAdd(&A.gcount[G_PACKED] + (d == ~0ull ? 1 : 0),
                                                                    ((unsigned long long)ne << 32) | ni)
                                                        : 0ull;
                     S.e0 = got >> 32;
@@ -1733,7 +1733,7 @@ DEV void bin_body(const BinArgs& A) {
 #endif
                 {
                 const unsigned long long got =
-                    tot ? atomicAdd(&A.gcount[0], ((unsigned long long)ne << 32) | ni) : 0ull;
+                    tot ? atomicAdd(&A.gcount[G_PACKED], ((unsigned long long)ne << 32) | ni) : 0ull;
                 S.e0 = got >> 32;
                 S.i0 = got & 0xFFFFFFFFull;
                 }
@@ -1827,7 +1827,7 @@ DEV void bin_body(const BinArgs& A) {
                     bm_ok = bm_check(A.e_off, A.e_cnt, S, cnt, per, e0, i0, n_ent, (uint32_t)ex_l, 0u, n_long, bm, W);
                     if (bm_ok) bm_emit(A.ids_out, A.read_ids, A.id_off, i0, 0u, n_long, bm, W, offs, tile, R, A.rord + lo);
                     PROF_MARK(19);
-                    if (tid == 0 && A.pstat) atomicAdd(&A.pstat[10], 1ull);
+                    if (tid == 0 && A.pstat) atomicAdd(&A.pstat[PS_BITMAP], 1ull);
                 } else {
                     const uint32_t G = fixed + W <= win_cap ? (win_cap - fixed) / W : 0u;
                     bm_ok = G && (n_long + G - 1u) / G <= RANK_GROUPS &&
@@ -1836,7 +1836,7 @@ DEV void bin_body(const BinArgs& A) {
                                              R, A.rord + lo PROF_ARGS);
                 }
                 if (bm_ok) {
-                    if (!merged && tid == 0 && A.pstat) atomicAdd(&A.pstat[10], 1ull);
+                    if (!merged && tid == 0 && A.pstat) atomicAdd(&A.pstat[PS_BITMAP], 1ull);
                 } else {
                     // ranks at their cursors, then the long lists' id range mapped
                     // to ordinals in one coalesced pass (no gather inside the
@@ -2000,7 +2000,7 @@ __global__ __launch_bounds__(BIN_THREADS) void bin_parts_kernel(const BinArgs* _
 // takes items i, i + grid, ... (near-equal items; a shared claim counter cost
 // ~60 ns per serialised returning atomic, 0.13 ms for an empty launch)
 DEV bool fb_claim(const BinArgs& A, bool flat_only, unsigned long long& it, uint32_t& b, uint32_t& c) {
-    const unsigned long long n = A.flat_n[2];
+    const unsigned long long n = A.flat_n[FN_BUILD];
     for (; it < n; it += gridDim.x) {
         b = A.chunk_bin[it];
         if (flat_only && (A.flat_l0[b] & SPLIT_BIT)) continue;
@@ -2085,7 +2085,7 @@ __global__ __launch_bounds__(FB_THREADS) void flat_count_kernel(BinArgs A) {
 // bin's stage range) and, for a flat bin, the scatter cursors
 __global__ __launch_bounds__(1024) void flat_scan_kernel(BinArgs A) {
     __shared__ uint64_t red[16];
-    const uint32_t nf = (uint32_t)min<unsigned long long>(*A.flat_n, A.max_bins);
+    const uint32_t nf = (uint32_t)min<unsigned long long>(A.flat_n[FN_BINS], A.max_bins);
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     for (uint32_t q = blockIdx.x; q < nf; q += gridDim.x) {
         const uint32_t b = A.flat_list[q];
@@ -2268,7 +2268,7 @@ __global__ __launch_bounds__(FSL_THREADS) void flat_scatter_lds_kernel(BinArgs A
     uint16_t* const spart = reinterpret_cast<uint16_t*>(gbase + FSL_NP);  // [E]
     __shared__ uint32_t s_b, s_c, s_ok, s_seg, s_tot;
     __shared__ uint32_t red[FSL_THREADS / 64];
-    if (!A.flat_n[6]) return;  // no bin with that many partitions this time
+    if (!A.flat_n[FN_STAGED]) return;  // no bin with that many partitions this time
     const uint32_t tid = threadIdx.x;
     const int lane = (int)(tid & 63u), wid = (int)(tid >> 6);
     unsigned long long it = blockIdx.x;

@@ -1,13 +1,17 @@
 // kbin_internal.h -- declarations shared by the kernel files (kbin_kernels.hip:
 // the table engine and the common passes; kbin_sk.hip, kbin_plan.hip,
 // kbin_bins.hip, kbin_lists.hip: the binned engine; kbin_digest.hip) and the
-// host side (kbin_api.hip, kbin_group.hip): argument structs, record and map
-// layouts, launchers.  Not installed.
+// host side (kbin_api.hip, kbin_route.hip, kbin_bmap.hip, kbin_finalize.hip --
+// their own header is kbin_host.h -- and kbin_group.hip): argument structs,
+// record and map layouts, launchers; the shared counter words are in
+// kbin_words.h.  Not installed.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <initializer_list>
+
+#include "kbin_words.h"
 
 namespace kb {
 
@@ -146,7 +150,7 @@ struct BucketArgs {
     int bases_ready;           // bbase already written (bucket_stats_kernel after the record pass)
     int sub;                   // records carry their context sub-bin (sub_room): group by (mmer, sub-bin)
     uint32_t* bocc;            // [max_bins] k-mer occurrences of the bin (0: not counted), or null
-    unsigned long long* bin_ctr;   // bins (zeroed; = totals[2])
+    unsigned long long* bin_ctr;   // bins (zeroed; = totals[T_BINS])
     uint32_t* bstart;          // [max_bins] first record of bin
     uint32_t* bcount;          // [max_bins] records of bin
     uint32_t* bmmer;           // [max_bins] the bin's canonical mmer
@@ -280,8 +284,7 @@ struct BinArgs {
     // bin into flat per-partition lists (published below); phase 1 sweeps the
     // published partitions, any block any partition
     KB_G uint32_t* flat_list;            // [max_bins] published heavy bins
-    KB_G unsigned long long* flat_n;     // (zeroed) [0] published bins [1] pool [2] build items,
-                                    // claims: [3] count [4] scatter [5] phase 1
+    KB_G unsigned long long* flat_n;     // (zeroed) the FN_* words (kbin_words.h)
     KB_G uint32_t* flat_next;            // [max_bins] next partition to claim
     KB_G uint32_t* flat_l0;              // [max_bins] partition depth
     KB_G unsigned long long* flat_sbase; // [max_bins] stage base
@@ -299,7 +302,7 @@ struct BinArgs {
     uint64_t split_occ;             // (set at launch)
     uint32_t big_div;               // flat lists for a multi-table bin above n_occ / (blocks x big_div)
     uint64_t big_occ;               // (set at launch; 0 = by depth only)
-    KB_G const uint64_t* totals;    // totals[2] = nbins
+    KB_G const uint64_t* totals;    // totals[T_BINS] = nbins
     int K, M;
     uint32_t keep_gt;
     uint32_t ts_log2;
@@ -320,7 +323,7 @@ struct BinArgs {
     uint64_t heavy_hint;       // heavy / split bins the last finalize published (0: small grids for their kernels)
     int ablate;                // diagnostic builds (KB_BIN_PROF / KB_BIN_ABL) only: 1 expansion only,
                                // 2 no staging, 3 no id windows, 4 windows without sorts
-    KB_G unsigned long long* gcount;  // [0] entries << 32 | ids  [2] distinct keys before prune
+    KB_G unsigned long long* gcount;  // the G_* words (kbin_words.h)
     KB_G uint32_t* status;
     KB_G uint32_t* e_mmer;
     KB_G uint64_t* e_hi;
@@ -351,13 +354,7 @@ struct BinArgs {
     uint32_t fs_lds;           // 1: heavy bins with 9..2048 partitions write their lists LDS-staged
     float rho_tab;             // expected table keys per occurrence under the pre-filter
     KB_G unsigned long long* tab_keys;  // (zeroed) keys that entered a table
-    // (zeroed) path counters for kb_timing, one atomic per bin or partition:
-    // [0] heavy bins published as flat lists [1] split bins published
-    // [2] partitions swept to their prune [3] partitions redone split (overflow)
-    // [4] deepest partition depth (max) [5] keys kept out by the pre-filter
-    // [6] offset-range partitions [7] partitions swept from flat lists
-    // [8] light pre-filtered bins [9] ranked bins [10] partitions emitted from rank bitmaps
-    KB_G unsigned long long* pstat;
+    KB_G unsigned long long* pstat;  // (zeroed) path counters for kb_timing: the PS_* words (kbin_words.h)
     uint32_t ts_adapt;         // 1: one-table light bins take the smallest table for their keys (KB_BIN_TS_ADAPT)
     uint32_t ldsbar;           // 1: barriers that order LDS only skip the global-store drain (KB_BIN_LDSBAR)
     uint32_t corrupt;          // diagnostic (KB_DIAG_CORRUPT=1): block 0 adds one to a count, so the
@@ -378,14 +375,13 @@ struct BinArgs {
     KB_G uint32_t* rrank;           // [R] record -> rank in its bin
     KB_G uint32_t* rord;            // [R] (bin start + rank) -> ordinal
 };
-constexpr int KB_PSTAT = 11;
 // light pre-filtered bins (kbin_bins.hip): the per-bin sketch's cells and the
 // distinct-key load it takes (the host sizes sub-bins by them)
 constexpr uint32_t PFL_CELLS = 8192u * 16u;
-constexpr double PFL_LOAD = 0.15;  // (h_totals[16 .. 16 + KB_PSTAT) in the stats copy)
+constexpr double PFL_LOAD = 0.15;
 
 struct ListArgs {
-    const uint64_t* totals;    // totals[0] = entries
+    const uint64_t* totals;    // totals[T_ENTRIES] = entries
     const uint32_t* e_cnt;
     const uint64_t* e_off;
     uint32_t* ids_ord;         // call ordinals per list (scratch for long lists)
@@ -494,18 +490,16 @@ struct ClearList {
     }
 };
 hipError_t launch_clear(const ClearList& l, hipStream_t s);
-// totals[12] = sum of the NB bucket fills (records), totals[13] = the largest,
-// totals[14] = status word misc[0]: the record pass's results in one copy;
-// totals[8] += the nk per-block k-mer sums kpart (the record pass's N)
+// the record pass's results in one copy: totals[T_REC_SUM], [T_REC_MAX] from the
+// NB bucket fills, [T_REC_STATUS] = misc[M_REC_STATUS]; totals[T_KMERS] += the
+// nk per-block k-mer sums kpart (the record pass's N)
 hipError_t launch_bucket_stats(const unsigned long long* bfill, uint32_t NB, const uint32_t* misc, uint64_t* totals,
                                uint64_t cap, const uint64_t* rbase, uint64_t* bbase, const unsigned long long* kpart,
                                uint64_t nk, hipStream_t s);
-// report (non-null): the finalize's stats in one copy -- totals[16 ..
-// 16 + KB_PSTAT) = pstat, totals[28 .. 31) = misc[0 .. 6) in pairs
+// report_misc (non-null): the finalize's stats in one copy, totals' report block (kbin_words.h)
 hipError_t launch_bins_final(const unsigned long long* gcount, uint64_t* e_off, uint64_t* totals,
                              uint64_t max_entries, const unsigned long long* flat_n, const unsigned long long* lq_n,
                              const unsigned long long* pstat, const uint32_t* report_misc, hipStream_t s);
-constexpr int KB_TOTALS = 32;  // device totals words (the report layout above)
 
 // launch helpers implemented in kbin_kernels.hip (all asynchronous on `s`)
 hipError_t launch_pack(const uint8_t* d_bases, const uint64_t* d_off, uint64_t n_reads,

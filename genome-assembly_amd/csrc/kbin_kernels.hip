@@ -915,7 +915,7 @@ __global__ __launch_bounds__(256) void os_scatter_kernel(const uint64_t* __restr
 
 uint64_t onesweep_flag_elems(uint64_t n) { return 256ull * ((n + RS_TILE - 1) / RS_TILE); }
 
-// aux: [0, 4*256) digit histograms -> bases, [1024, 1028) tickets, [1028] error
+// aux: the OS_AUX_* layout (kbin_words.h)
 hipError_t launch_onesweep(uint64_t* a, uint64_t* b, uint64_t n, int key_bits, uint64_t* flags,
                            uint32_t* aux, uint32_t* epoch, uint64_t** sorted, hipStream_t s) {
     *sorted = a;
@@ -924,7 +924,7 @@ hipError_t launch_onesweep(uint64_t* a, uint64_t* b, uint64_t n, int key_bits, u
     const int npass = (key_bits + 7) / 8;
     if (npass > OS_MAX_PASSES) return hipErrorInvalidValue;
     const uint32_t n_tiles = (uint32_t)((n + RS_TILE - 1) / RS_TILE);
-    hipError_t e = hipMemsetAsync(aux, 0, (4 * 256 + 8) * sizeof(uint32_t), s);
+    hipError_t e = hipMemsetAsync(aux, 0, OS_AUX_WORDS * sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(os_hist_kernel, dim3(1024), dim3(256), 0, s, a, (uint32_t)n, npass, aux);
     hipLaunchKernelGGL(os_bases_kernel, dim3(1), dim3(256), 0, s, aux, npass);
@@ -933,7 +933,7 @@ hipError_t launch_onesweep(uint64_t* a, uint64_t* b, uint64_t n, int key_bits, u
     for (int p = 0; p < npass; p++) {
         const uint32_t ep = ++*epoch;
         hipLaunchKernelGGL(os_scatter_kernel, dim3(n_tiles), dim3(256), 0, s, src, dst, (uint32_t)n,
-                           32 + 8 * p, aux + p * 256, flags, aux + 1024 + p, ep, aux + 1028);
+                           32 + 8 * p, aux + p * 256, flags, aux + OS_AUX_TICKETS + p, ep, aux + OS_AUX_ERR);
         uint64_t* t = src;
         src = dst;
         dst = t;
@@ -1065,13 +1065,13 @@ __global__ void runs_total_kernel(const uint64_t* __restrict__ tot_runs, uint64_
                                   uint32_t* __restrict__ starts, uint64_t* __restrict__ totals,
                                   uint64_t max_runs) {
     uint64_t D = *tot_runs;
-    totals[3] = 0;
+    totals[T_BIN_OVER] = 0;
     if (D > max_runs) {  // cannot happen (runs == distinct keys); never write out of bounds
-        totals[3] = D;
+        totals[T_BIN_OVER] = D;
         D = max_runs;
     }
     starts[D] = (uint32_t)n;
-    totals[2] = D;
+    totals[T_BINS] = D;
 }
 
 // per run: kept flag / kept length partials
@@ -1080,7 +1080,7 @@ __global__ __launch_bounds__(256) void runs_partials_kernel(const uint32_t* __re
                                                             uint32_t keep_gt, uint64_t* __restrict__ part,
                                                             uint64_t nb) {
     __shared__ uint64_t sh[4];
-    const uint64_t D = totals[2];
+    const uint64_t D = totals[T_BINS];
     const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE;
     uint64_t nk = 0, ni = 0;
     if (base < D) {
@@ -1117,7 +1117,7 @@ __global__ __launch_bounds__(256) void runs_write_kernel(
     __shared__ uint32_t rs[257];   // run starts of the round (+ end)
     __shared__ uint32_t ro[256];   // id offset of each run, NONE if pruned
     __shared__ uint8_t rofk[RUN_SPAN];  // run (within the round) of each record of the span
-    const uint64_t D = totals[2];
+    const uint64_t D = totals[T_BINS];
     const uint64_t base = (uint64_t)blockIdx.x * SCAN_TILE;
     if (base >= D) return;  // uniform per block
     uint64_t ent = part[blockIdx.x];
@@ -1191,12 +1191,12 @@ __global__ __launch_bounds__(256) void runs_write_kernel(
 
 __global__ void entries_total_kernel(const uint64_t* __restrict__ tk, const uint64_t* __restrict__ ti,
                                      uint64_t* __restrict__ e_off, uint64_t* __restrict__ totals) {
-    totals[0] = *tk;
-    totals[1] = *ti;
+    totals[T_ENTRIES] = *tk;
+    totals[T_IDS] = *ti;
     e_off[*tk] = *ti;
 }
 
-// run starts of a sorted record array (key = bits 32..): starts[0..D], D in d_totals[2]
+// run starts of a sorted record array (key = bits 32..): starts[0..D], D in d_totals[T_BINS]
 hipError_t launch_heads(const uint64_t* S, uint64_t n, uint32_t* starts, uint64_t max_runs,
                         uint64_t* scratch, uint64_t scratch_n, uint64_t* d_totals, hipStream_t s,
                         int key_shift) {
@@ -1221,7 +1221,7 @@ hipError_t launch_runs(const uint64_t* S, uint64_t n, const uint64_t* table, int
     const uint64_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
     const uint64_t nbr = (max_runs + SCAN_TILE - 1) / SCAN_TILE;
     if (scratch_n < std::max(nb + 1, 2 * nbr + 2)) return hipErrorInvalidValue;
-    if (n == 0) {  // (totals[3], the run-overflow word, too: the host checks it)
+    if (n == 0) {  // (totals[T_BIN_OVER], the run-overflow word, too: the host checks it)
         hipError_t e = hipMemsetAsync(d_totals, 0, 4 * sizeof(uint64_t), s);
         if (e == hipSuccess) e = hipMemsetAsync(e_off, 0, sizeof(uint64_t), s);
         return e;

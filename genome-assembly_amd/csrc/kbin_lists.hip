@@ -47,7 +47,7 @@ __global__ __launch_bounds__(LIST_THREADS) __attribute__((amdgpu_waves_per_eu(5,
     __shared__ uint32_t n_big, n_mid, s_long, w_lo[2], w_hi[2];
     const uint32_t tid = threadIdx.x;
     const int lane = tid & 63, wid = tid >> 6;
-    const uint64_t n_entries = A.totals[0];
+    const uint64_t n_entries = A.totals[T_ENTRIES];
     // items: the bin kernels' queue (partitions whose ids took the global
     // path, and long lists of the LDS path), else every entry in chunks of 256
     // (an entry-capacity overflow publishes no entries, bins_final_kernel: the

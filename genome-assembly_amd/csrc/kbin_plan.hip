@@ -24,7 +24,7 @@ __global__ __launch_bounds__(1024) void bins_order_kernel(const uint32_t* __rest
                                                           uint32_t* __restrict__ order, uint64_t max_bins) {
     constexpr uint32_t NC = 256;
     __shared__ uint32_t hist[NC];
-    const uint32_t nbins = (uint32_t)min(totals[2], max_bins);
+    const uint32_t nbins = (uint32_t)min(totals[T_BINS], max_bins);
     for (uint32_t i = threadIdx.x; i < NC; i += 1024) hist[i] = 0;
     __syncthreads();
     for (uint32_t b = threadIdx.x; b < nbins; b += 1024) atomicAdd(&hist[order_class(bcount[b])], 1u);
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(1024) void bins_desc_kernel(const uint32_t* __restr
                                                          const uint64_t* __restrict__ totals, uint64_t max_bins,
                                                          uint4* __restrict__ desc, unsigned long long* stage_ctr) {
     __shared__ uint64_t red[16];
-    const uint32_t nbins = (uint32_t)min(totals[2], max_bins);
+    const uint32_t nbins = (uint32_t)min(totals[T_BINS], max_bins);
     const uint32_t per = (nbins + 1023u) / 1024u, i0 = threadIdx.x * per;
     uint64_t mine = 0;
     for (uint32_t k = 0; k < per; k++)
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(1024) void bins_plan_kernel(const uint32_t* __restr
     __shared__ uint64_t red[16];
     const uint32_t t = threadIdx.x;
     const int lane = (int)(t & 63u), wid = (int)(t >> 6);
-    const uint32_t nbins = (uint32_t)min(totals[2], max_bins);
+    const uint32_t nbins = (uint32_t)min(totals[T_BINS], max_bins);
     if (t < NC) hist[t] = 0;
     __syncthreads();
     for (uint32_t b = t; b < nbins; b += 1024) atomicAdd(&hist[order_class(bcount[b])], 1u);
@@ -190,7 +190,7 @@ __global__ __launch_bounds__(256) void bins_describe_kernel(const uint64_t* __re
                                                             const uint64_t* __restrict__ totals,
                                                             uint32_t* __restrict__ bcount,
                                                             uint32_t* __restrict__ bmmer, uint64_t max_bins) {
-    const uint64_t nbins = min(totals[2], max_bins);
+    const uint64_t nbins = min(totals[T_BINS], max_bins);
     for (uint64_t b = blockIdx.x * 256ull + threadIdx.x; b < nbins; b += (uint64_t)gridDim.x * 256) {
         bcount[b] = starts[b + 1] - starts[b];
         bmmer[b] = (uint32_t)(keys[starts[b]] >> 38);
@@ -452,19 +452,20 @@ __global__ void bins_final_kernel(const unsigned long long* gcount, uint64_t* e_
                                   const unsigned long long* lq_n, const unsigned long long* pstat,
                                   const uint32_t* misc) {
     if (pstat)  // (the finalize's stats next to the totals: one copy, kbin_internal.h)
-        for (int k = 0; k < KB_PSTAT; k++) totals[16 + k] = pstat[k];
+        for (int k = 0; k < KB_PSTAT; k++) totals[T_PSTAT + k] = pstat[k];
     if (misc)
-        for (int k = 0; k < 3; k++) totals[28 + k] = (uint64_t)misc[2 * k] | ((uint64_t)misc[2 * k + 1] << 32);
+        for (int k = 0; k < M_REPORTED / 2; k++)
+            totals[T_MISC_PAIRS + k] = (uint64_t)misc[2 * k] | ((uint64_t)misc[2 * k + 1] << 32);
     // (the next finalize's grid hints: published heavy / split bins, queued list items)
-    totals[12] = flat_n ? flat_n[0] : 0ull;
-    totals[13] = lq_n ? *lq_n : 0ull;
+    totals[T_HEAVY] = flat_n ? flat_n[FN_BINS] : 0ull;
+    totals[T_QUEUED] = lq_n ? *lq_n : 0ull;
     // on overflow the counters ran past the capacity (status says so) and the
     // bins past it wrote nothing, so no entry range is whole: publish none (the
     // lists kernel then has no work and the host reruns at the exact need)
-    const uint64_t ne0 = gcount[0] >> 32, ni = gcount[0] & 0xFFFFFFFFull;
+    const uint64_t ne0 = gcount[G_PACKED] >> 32, ni = gcount[G_PACKED] & 0xFFFFFFFFull;
     const uint64_t ne = ne0 <= max_entries ? ne0 : 0;
-    totals[0] = ne;
-    totals[1] = ni;
+    totals[T_ENTRIES] = ne;
+    totals[T_IDS] = ni;
     e_off[ne] = ni;
 }
 
@@ -521,10 +522,10 @@ __global__ __launch_bounds__(1024) void bucket_stats_kernel(const unsigned long 
     if (t < NB) bbase[t] = wp + inc - v;
     if (t == 0) {
         bbase[NB] = tot;
-        totals[8] += kt;
-        totals[12] = sum;
-        totals[13] = mx;
-        totals[14] = misc[0];
+        totals[T_KMERS] += kt;
+        totals[T_REC_SUM] = sum;
+        totals[T_REC_MAX] = mx;
+        totals[T_REC_STATUS] = misc[M_REC_STATUS];
     }
 }
 

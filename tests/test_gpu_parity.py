@@ -932,7 +932,7 @@ def test_edge_inputs_and_context_reuse(engine):
 
 def test_speculative_bucket_layout():
     """The bucket ordering goes out before the finalize's mid-way wait, in a
-    layout sized from the last pass's records (kbin_api.hip bucket_phase).
+    layout sized from the last pass's records (kbin_finalize.hip bucket_phase).
     One context: a pass, then one with 3x the records (the layout is too
     small: the ordering reruns exactly), then the same again (the speculative
     ordering stands) -- each bit-exact against the oracle."""
